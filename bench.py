@@ -1,6 +1,6 @@
 """bench.py - throughput of the MI355X-native `MoGeModel.infer()` hot path (driver contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is ONE infer() pass of the hot path over one batch of synthetic images that are already resident in HBM.
 Workload (BASELINE.json metric: images/sec, moge-2-vitl 518x518 fp16): configs[2] = moge-2-vitl (no normal head),
@@ -225,10 +225,51 @@ class PowerSampler:
                 "note": "sampled during an untimed repeat of the same steps right after the timed region (this rank's GPU)"}
 
 
+DUMP_BYTES = 60_000_000          # --dump-outputs: under 64 MB with the .npy headers
+
+
+def dump_outputs(outs, d, budget=DUMP_BYTES):
+    """Write the outputs of one step (a list with one infer() dict per sub-batch) as d/<key>.npy, or d/<key>_<i>.npy for several
+    sub-batches, all float32 (the mask as 0 / 1).  Per-image arrays (intrinsics, metric_scale) are written whole.  If the per-pixel maps
+    (points, depth, mask, normal) would exceed `budget` bytes in all, each is cut to the same seeded sample of pixels (seed 0, sorted
+    flat (b, y, x) indices), shape (n,) or (n, 3): the sample depends only on the shapes, so equal arguments give equal files.
+    infer() marks the pixels its mask rejects with inf in points / depth (apply_mask, as the reference); those are written as 0 - mask.npy
+    says which pixels they are - so that every file is finite.  A non-finite value at a pixel the mask keeps is written as it is."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    maps = ("points", "depth", "mask", "normal")
+    full = sum(v.numel() * 4 for o in outs for k, v in o.items() if k in maps)
+    per_image = sum(v.numel() * 4 for o in outs for k, v in o.items() if k not in maps)
+    frac = min(1.0, (budget - per_image) / full) if full else 1.0
+    nonfinite = []
+    for i, o in enumerate(outs):
+        m = o.get("mask")
+        for k, v in o.items():
+            v = v.float()
+            if m is not None and k in maps and k != "mask":
+                keep = m if v.dim() == m.dim() else m[..., None]
+                v = torch.where(keep | torch.isfinite(v), v, torch.zeros_like(v))
+            if k in maps and frac < 1.0:
+                B, H, W = v.shape[:3]
+                n = int(B * H * W * frac)
+                g = torch.Generator(device="cpu").manual_seed(0)
+                idx = torch.randperm(B * H * W, generator=g)[:n].sort().values.to(v.device)
+                v = v.reshape(B * H * W, -1).index_select(0, idx).squeeze(-1)
+            name = k if len(outs) == 1 else f"{k}_{i}"
+            a = np.ascontiguousarray(v.cpu().numpy(), dtype=np.float32)
+            if not np.isfinite(a).all():
+                nonfinite.append(name)
+            np.save(os.path.join(d, name + ".npy"), a)
+    if nonfinite:
+        print(f"[bench] WARNING: --dump-outputs: non-finite values at pixels the mask keeps in {nonfinite}", file=sys.stderr)
+    print(f"[bench] --dump-outputs: {sum(len(o) for o in outs)} arrays of the last timed step in {d} "
+          f"({'every pixel' if frac >= 1.0 else f'a seeded sample of {frac:.3f} of the pixels'})", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU)
     ap.add_argument("--config", default=WORKLOAD_CONFIG)
@@ -248,7 +289,11 @@ def main():
                                                                                "host-staged weight broadcast, for ranks that must share a device)")
     ap.add_argument("--single-device", action="store_true", help="every rank drives cuda:0 (start-up / host-feeding test of the N-process path on a 1-GPU box; "
                                                                  "needs --backend gloo: RCCL refuses two ranks on one device).  The line says so; it is not a scaling number")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the run, write what the timed path returned in its last step as "
+                                                                        "DIR/<name>.npy (float32; rank 0; a fixed seeded pixel sample above 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_baseline_only:
         # no GPU needed: the CPU leg alone (in the build container this times the unmodified reference: kind "reference")
         from oracle import moge_oracle as O
@@ -269,7 +314,8 @@ def main():
         # not under a launcher yet: become `python -m torch.distributed.run ... bench.py <same arguments>` (one rank per GPU over RCCL)
         env = dict(os.environ)
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execvpe(sys.executable, self_launch_command(sys.argv[1:], args.gpus), env)
+        import subprocess                                  # a child process, not exec: this one keeps no GPU state to hand over
+        raise SystemExit(subprocess.call(self_launch_command(sys.argv[1:], args.gpus), env=env))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     import torch.distributed as dist
@@ -344,10 +390,8 @@ def main():
         torch.cuda.synchronize(dev)
 
     def step():
-        o = None
-        for xi in xs:               # one step = one infer() per same-shape sub-batch (the reference cannot mix shapes in a tensor)
-            o = model.infer(xi, **kw)
-        return o
+        # one step = one infer() per same-shape sub-batch (the reference cannot mix shapes in a tensor); returns every sub-batch's outputs
+        return [model.infer(xi, **kw) for xi in xs]
 
     for _ in range(args.warmup):
         step()
@@ -401,7 +445,7 @@ def main():
         if rccl is not None:
             rccl["startup_seconds_max_over_ranks"] = round(startup_max, 2)
             rccl["startup_seconds_per_rank"] = per_rank
-    assert bool(torch.isfinite(out["intrinsics"]).all())
+    assert bool(torch.isfinite(out[-1]["intrinsics"]).all())
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -574,6 +618,8 @@ def main():
                                            "model.half() of the resident fp32 master (what every rank does after the one-time broadcast)"}
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(O, cfg, sd, x[:1].float().cpu(), kw, args.config, num_tokens)
+        if args.dump_outputs:
+            dump_outputs(out, args.dump_outputs)
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

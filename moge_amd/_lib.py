@@ -9,6 +9,7 @@ import torch  # noqa: F401  (must be imported first: libmoge_hip.so binds to the
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libmoge_hip.so")
+EXPERIMENTS_LIB_PATH = os.path.join(HERE, "lib", "experiments", "libmoge_hip.so")     # -DMOGE_EXPERIMENTS copy (tests of the rejected kernels)
 
 MOGE_MAX_TAPS = 8
 MOGE_LEVELS = 5
@@ -88,11 +89,11 @@ class MogeError(RuntimeError):
     pass
 
 
-def _load() -> C.CDLL:
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(f"{LIB_PATH} is missing: build it with `python -m moge_amd.build` (hipcc, gfx950). "
+def _load(path: str = LIB_PATH, mode: int = C.RTLD_GLOBAL) -> C.CDLL:
+    if not os.path.exists(path):
+        raise ImportError(f"{path} is missing: build it with `python -m moge_amd.build` (hipcc, gfx950). "
                           "moge_amd has no CPU / PyTorch fallback.")
-    lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
+    lib = C.CDLL(path, mode=mode)
     vp, i32, i64, f32p = C.c_void_p, C.c_int, C.c_int64, C.c_void_p
     sig = {
         "moge_abi_version": (C.c_int, []),
@@ -149,6 +150,16 @@ def _load() -> C.CDLL:
 
 
 lib = _load()
+_experiments_lib = None
+
+
+def experiments_lib() -> C.CDLL:
+    """The --experiments copy of the library (moge_amd.build.build_experiments), loaded RTLD_LOCAL beside `lib`: it is linked -Bsymbolic, so its
+    calls stay inside it.  Tests swap it in for `lib` to reach the superseded kernel variants; the product path never loads it."""
+    global _experiments_lib
+    if _experiments_lib is None:
+        _experiments_lib = _load(EXPERIMENTS_LIB_PATH, C.RTLD_LOCAL)
+    return _experiments_lib
 EXPORTS = ["moge_abi_version", "moge_last_error", "moge_create", "moge_create_v1", "moge_v1_forward", "moge_v1_infer", "moge_destroy", "moge_load_weights", "moge_alloc_master",
            "moge_master_blob", "moge_master_ready", "moge_broadcast_weights", "moge_set_precision", "moge_set_onnx_compatible_mode", "moge_workspace_bytes", "moge_forward", "moge_infer",
            "moge_postprocess", "moge_depth_edge_mask", "moge_cast_f16", "moge_sync", "moge_profile_enable", "moge_profile_read", "moge_debug_tap", "moge_tune_set", "moge_test_gemm",

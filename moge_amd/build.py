@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmoge_hip.so")
+EXPERIMENTS_LIBDIR = os.path.join(LIBDIR, "experiments")     # build_experiments(): the -DMOGE_EXPERIMENTS copy the tests load beside LIB
 SOURCES = ["gemm.hip", "gemm_pp.hip", "conv_pp.hip", "attention.hip", "attention_pp.hip", "elementwise.hip", "post.hip", "alignment.hip", "model.hip", "test_api.hip"]
 EXPERIMENT_SOURCES = ["conv_rb.hip"]      # tools/experiments/: the fused residual block (slower than the two conv_pp launches; kbench / A-B only)
 HEADERS = ["common.h", "launchers.h", os.path.join("..", "..", "include", "moge_hip.h")]
@@ -33,21 +34,22 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True, experiments: bool = False) -> str:
+def build(force: bool = False, verbose: bool = True, experiments: bool = False, libdir: str = LIBDIR, symbolic: bool = False) -> str:
     """experiments=True adds -DMOGE_EXPERIMENTS: the superseded / rejected kernel variants under tools/experiments/ are compiled in and become
-    selectable through MOGE_PP_EXP / MOGE_ATTN_EXP / ... (tools/kbench A-B timing only; the product library is built without them)."""
+    selectable through MOGE_PP_EXP / MOGE_ATTN_EXP / ... (tools/kbench A-B timing only; the product library is built without them).
+    libdir: where libmoge_hip.so and its objects go; symbolic: link -Bsymbolic (a copy loaded beside the product library keeps its own calls)."""
     hipcc = _hipcc()
     flags = FLAGS + (["-DMOGE_EXPERIMENTS"] if experiments else [])
-    stamp = os.path.join(LIBDIR, "obj", ".experiments")
-    os.makedirs(os.path.join(LIBDIR, "obj"), exist_ok=True)
+    lib_path = os.path.join(libdir, "libmoge_hip.so")
+    stamp = os.path.join(libdir, "obj", ".experiments")
+    os.makedirs(os.path.join(libdir, "obj"), exist_ok=True)
     if os.path.exists(stamp) != experiments:                # switching flavour rebuilds everything
         force = True
         if experiments:
             open(stamp, "w").close()
         else:
             os.remove(stamp)
-    os.makedirs(LIBDIR, exist_ok=True)
-    objdir = os.path.join(LIBDIR, "obj")
+    objdir = os.path.join(libdir, "obj")
     os.makedirs(objdir, exist_ok=True)
     hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
     if experiments:
@@ -73,9 +75,15 @@ def build(force: bool = False, verbose: bool = True, experiments: bool = False) 
 
     with ThreadPoolExecutor(max_workers=min(6, max(1, len(jobs)))) as ex:
         list(ex.map(run, jobs))
-    if force or jobs or _stale(LIB, objs):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs)
-    return LIB
+    if force or jobs or _stale(lib_path, objs):
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + (["-Wl,-Bsymbolic"] if symbolic else []) + ["-o", lib_path] + objs)
+    return lib_path
+
+
+def build_experiments(force: bool = False, verbose: bool = True) -> str:
+    """The -DMOGE_EXPERIMENTS library in moge_amd/lib/experiments/, beside (not instead of) the product library: the tests of the superseded
+    kernel variants load it through moge_amd._lib.experiments_lib()."""
+    return build(force=force, verbose=verbose, experiments=True, libdir=EXPERIMENTS_LIBDIR, symbolic=True)
 
 
 def build_tools(verbose: bool = True, experiments: bool = None) -> str:

@@ -16,9 +16,9 @@ there); what differs is forced by what this image ships:
   * utils3d is not installed (un-vendored dependency, pyproject.toml:23): the icosahedron, the look-at extrinsics (OpenCV camera: x right,
     y down, z forward; world up = +z) and the uv / pixel conventions (pixel-centre uv in [0, 1], pixel = uv * size - 0.5) are restated.
     Pinned to the reference's own module all the same: oracle/make_panorama_golden.py runs the unmodified moge/utils/panorama.py with cv2 / utils3d
-    stand-ins built from the helpers below and stores its outputs (tests/golden/panorama_ref.npz); tests/test_panorama_reference.py holds this file
-    to them - merged log-distance within 5e-5 (observed 1e-5 ... 1e-6), masks equal, the uint8 split within 1 LSB - and re-runs the reference live
-    where /root/reference exists.  What stays unpinned is the utils3d CONVENTION itself (the same stand-in serves both sides), as for the other
+    stand-ins built from the helpers below and stores its outputs (tests/golden/panorama_ref.npz, panorama_spherical_ref.npz);
+    tests/test_panorama_reference.py holds this file to them - merged log-distance within 5e-5 (observed 1e-5 ... 1e-6), masks equal, the uint8
+    split within 1 LSB, the spherical maps within 1e-12.  What stays unpinned is the utils3d CONVENTION itself (the same stand-in serves both sides), as for the other
     utils3d call sites (README); tests/test_panorama_cpu.py additionally checks the pipeline against an analytic scene.
 """
 from __future__ import annotations

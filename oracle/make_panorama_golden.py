@@ -1,9 +1,9 @@
 """TEST INFRASTRUCTURE (not product): pins moge_amd/panorama.py to the reference's moge/utils/panorama.py.
 
 Runs the UNMODIFIED /root/reference/moge/utils/panorama.py (`merge_panorama_depth` :109-191, `split_panorama_image` :39-50,
-`get_panorama_cameras` :19-23) in this container and writes its outputs to tests/golden/panorama_ref.npz; tests/test_panorama_reference.py
-compares moge_amd.panorama with that file everywhere (the GPU box has no /root/reference) and, where the reference checkout exists, with the
-reference run live.
+`get_panorama_cameras` :19-23, `spherical_uv_to_directions` / `directions_to_spherical_uv`) and writes its outputs to
+tests/golden/panorama_ref.npz and tests/golden/panorama_spherical_ref.npz; tests/test_panorama_reference.py compares moge_amd.panorama with
+those files.  `--check` writes nothing: it runs the reference live and asserts that it still reproduces the committed files.
 
 The reference imports two packages this image does not ship.  They are replaced by the DOCUMENTED stubs below, exactly as
 oracle/make_golden.py::install_stubs does for `infer()`:
@@ -22,7 +22,8 @@ oracle/make_golden.py::install_stubs does for `infer()`:
 
 The stubs are built from moge_amd.panorama's private helpers on purpose: the point is to run the reference's code on the same primitives.
 
-    python oracle/make_panorama_golden.py          # rewrites tests/golden/panorama_ref.npz
+    python oracle/make_panorama_golden.py          # rewrites tests/golden/panorama_ref.npz and panorama_spherical_ref.npz
+    python oracle/make_panorama_golden.py --check  # the reference, run live, reproduces both committed files
 """
 import os
 import sys
@@ -33,6 +34,7 @@ import numpy as np
 REFERENCE_ROOT = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "..", "tests", "golden", "panorama_ref.npz")
+SPHERICAL_GOLDEN = os.path.join(HERE, "..", "tests", "golden", "panorama_spherical_ref.npz")
 
 
 def install_panorama_stubs():
@@ -172,9 +174,40 @@ def reference_outputs(ref, P):
     return out
 
 
+def spherical_inputs(P):
+    """A pixel-centre uv grid and seeded unit-free directions (float64) for the two spherical maps."""
+    return P._uv_grid(17, 31), np.random.default_rng(0).normal(size=(50, 3))
+
+
+def reference_spherical_outputs(ref, P):
+    uv, d = spherical_inputs(P)
+    return {"uv_to_directions": np.asarray(ref.spherical_uv_to_directions(uv), dtype=np.float64),
+            "directions_to_uv": np.asarray(ref.directions_to_spherical_uv(d), dtype=np.float64)}
+
+
+def check(ref, P):
+    """The reference, run live, reproduces the committed files (they are not stale)."""
+    live, gold = reference_outputs(ref, P), np.load(GOLDEN)
+    for k in gold.files:
+        a, b = live[k], gold[k]
+        if a.dtype == np.bool_ or a.dtype == np.uint8:
+            assert np.array_equal(a, b), k
+        elif k.endswith("_depth"):
+            assert np.abs(np.log(a) - np.log(b)).max() < 1e-6, k          # same code, same inputs (BLAS / thread order only)
+        else:
+            assert np.allclose(a, b, atol=1e-6), k
+    live, gold = reference_spherical_outputs(ref, P), np.load(SPHERICAL_GOLDEN)
+    for k in gold.files:
+        assert np.allclose(live[k], gold[k], atol=1e-12), k
+
+
 if __name__ == "__main__":
     ref = load_reference()
     from moge_amd import panorama as P
-    out = reference_outputs(ref, P)
-    np.savez_compressed(GOLDEN, **out)
-    print("wrote", os.path.normpath(GOLDEN), {k: (v.shape, str(v.dtype)) for k, v in out.items()})
+    if "--check" in sys.argv:
+        check(ref, P)
+        print("the reference reproduces", os.path.normpath(GOLDEN), "and", os.path.normpath(SPHERICAL_GOLDEN))
+        sys.exit(0)
+    for path, out in ((GOLDEN, reference_outputs(ref, P)), (SPHERICAL_GOLDEN, reference_spherical_outputs(ref, P))):
+        np.savez_compressed(path, **out)
+        print("wrote", os.path.normpath(path), {k: (v.shape, str(v.dtype)) for k, v in out.items()})

@@ -1,7 +1,21 @@
 """ctypes helpers for the per-kernel C-ABI test entry points (tests only)."""
+import contextlib
+
 import torch
 
 from moge_amd import _lib as L
+
+
+@contextlib.contextmanager
+def experiments_library():
+    """Every helper here, L.tune and L.check call the --experiments copy of the library (built by build() beside the product one) inside
+    the block, the product library again after it."""
+    prev = L.lib
+    L.lib = L.experiments_lib()
+    try:
+        yield
+    finally:
+        L.lib = prev
 
 
 def _p(t):

@@ -7,11 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import os
-
 pytestmark = pytest.mark.gpu
-EXPERIMENTS = os.path.exists(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "moge_amd", "lib", "obj", ".experiments"))
-needs_experiments = pytest.mark.skipif(not EXPERIMENTS, reason="tools/experiments/conv_rb.hip is compiled by `python -m moge_amd.build --experiments` only")
 
 
 @pytest.fixture(scope="module")
@@ -20,6 +16,13 @@ def H():
         pytest.skip("needs a GPU")
     from tests import hip_util
     return hip_util
+
+
+@pytest.fixture
+def X(H):
+    """hip_util on the --experiments copy of the library (tools/experiments/conv_rb.hip is compiled into that one only), for one test"""
+    with H.experiments_library():
+        yield H
 
 
 def r16(t):
@@ -83,8 +86,6 @@ def test_conv_fused_side_input(H, side_reg, B, Hh, Ww, Cin, Cout):
 @pytest.mark.parametrize("B,Hh,Ww,Cin,Cout", SHAPES[:4])
 def test_conv_uv_term(H, relu_in, act, B, Hh, Ww, Cin, Cout):
     """+ wu u(x) + wv v(y): the (u, v) input channels of the neck's input blocks as a rank-2 epilogue term (v2.py:154-160)."""
-    if relu_in and Cin != 64:
-        pytest.skip("ReLU prologue + uv: not a decoder combination")
     g, x, w, b = mk(B, Hh, Ww, Cin, Cout, 3)
     wu, wv = torch.randn(Cout, generator=g), torch.randn(Cout, generator=g)
     u = torch.linspace(-0.7, 0.7, Ww)
@@ -148,9 +149,8 @@ def resblock_ref(x, w1, b1, w2, b2):
     return r16(y) + x.cuda()
 
 
-@needs_experiments
 @pytest.mark.parametrize("B,Hh,Ww", [(2, 23, 45), (1, 16, 16), (3, 17, 70), (1, 5, 3), (2, 32, 48), (1, 50, 37), (1, 1, 1)])
-def test_fused_residual_block(H, B, Hh, Ww):
+def test_fused_residual_block(X, B, Hh, Ww):
     """conv_rb.hip: x + conv2(relu(conv1(relu(x)) + b1)) + b2 in ONE launch, the intermediate tile in LDS.  Against fp32 F.conv2d with the
     intermediate rounded to fp16 (what both paths store), on every border configuration (partial tiles right / bottom, images smaller than
     a tile, 1 x 1)."""
@@ -158,13 +158,12 @@ def test_fused_residual_block(H, B, Hh, Ww):
     w2 = r16(torch.randn(64, 64, 3, 3, generator=g) / (9 * 64) ** 0.5)
     b2 = torch.randn(64, generator=g)
     ref = resblock_ref(x, w1, b1, w2, b2)
-    out = H.conv_ex(x, w1, b1, w2=w2, bias2=b2)
+    out = X.conv_ex(x, w1, b1, w2=w2, bias2=b2)
     close(out, ref, "resblock")
 
 
-@needs_experiments
 @pytest.mark.parametrize("grid", [3, 13])
-def test_fused_residual_block_equals_two_launch_path_bitwise(H, grid):
+def test_fused_residual_block_equals_two_launch_path_bitwise(X, grid):
     """The fused kernel accumulates each conv in the two-launch kernels' order (same MFMA form, taps 0..8, two K-steps of 32) and rounds the
     intermediate and the output exactly where they do: BIT-identical results, with small workgroup caps (several tiles per workgroup, the
     fewer-workgroups-than-XCDs split) and with one tile per workgroup."""
@@ -173,13 +172,13 @@ def test_fused_residual_block_equals_two_launch_path_bitwise(H, grid):
     g, x, w1, b1 = mk(B, Hh, Ww, 64, 64, 6)
     w2 = r16(torch.randn(64, 64, 3, 3, generator=g) / (9 * 64) ** 0.5)
     b2 = torch.randn(64, generator=g)
-    h = H.conv_ex(x, w1, b1, relu_in=True, act=1)
-    two = H.conv_ex(h, w2, b2, add=x)
+    h = X.conv_ex(x, w1, b1, relu_in=True, act=1)
+    two = X.conv_ex(h, w2, b2, add=x)
     outs = []
     for cap in (grid, 1 << 20):
         L.tune("CONV_GRID", cap)
         try:
-            outs.append(H.conv_ex(x, w1, b1, w2=w2, bias2=b2))
+            outs.append(X.conv_ex(x, w1, b1, w2=w2, bias2=b2))
         finally:
             L.tune("CONV_GRID", 0)
     assert torch.equal(outs[0], outs[1])
@@ -199,11 +198,11 @@ def test_decoder_sized_maps(H, what):
         sw = r16(torch.randn(64, 64, generator=g) / 8)
         close(H.conv_ex(x, w, b, side=side, side_w=sw), conv_ref(x, w, b) + torch.einsum("bhwc,oc->bhwo", side.cuda(), sw.cuda()), what)
     elif what == "resblock":
-        if not EXPERIMENTS:
-            pytest.skip("fused residual block: --experiments builds only")
         w2 = r16(torch.randn(64, 64, 3, 3, generator=g) / 24)
         b2 = torch.randn(64, generator=g)
-        close(H.conv_ex(x, w, b, w2=w2, bias2=b2), resblock_ref(x, w, b, w2, b2), what)
+        with H.experiments_library():             # the fused residual block is compiled into the --experiments copy only
+            out = H.conv_ex(x, w, b, w2=w2, bias2=b2)
+        close(out, resblock_ref(x, w, b, w2, b2), what)
     else:
         up = F.interpolate(x.permute(0, 3, 1, 2).cuda(), scale_factor=2, mode="bilinear", align_corners=False)
         ref = F.conv2d(F.pad(up, (1, 1, 1, 1), mode="replicate"), w.cuda(), b.cuda()).permute(0, 2, 3, 1)

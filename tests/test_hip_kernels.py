@@ -26,6 +26,13 @@ def H():
     return hip_util
 
 
+@pytest.fixture
+def X(H):
+    """hip_util on the --experiments copy of the library (the superseded kernel variants of tools/experiments/), for one test"""
+    with H.experiments_library():
+        yield H
+
+
 @pytest.mark.parametrize("prec", [0, 1])
 @pytest.mark.parametrize("M,N,K,act", [(300, 256, 192, 0), (129, 64, 72, 1), (77, 32, 40, 0), (1000, 1152, 384, 2), (128, 128, 64, 0),
                                        (4097, 384, 1536, 0), (515, 96, 288, 0),
@@ -87,11 +94,9 @@ def test_attention_64_queries_per_wave_is_bit_identical(H, B, nh, N):
     assert torch.equal(outs[1], outs[2])
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "moge_amd", "lib", "obj", ".experiments")),
-                    reason="attn_pp16x_kernel (tools/experiments/) is compiled by `python -m moge_amd.build --experiments` only")
 @pytest.mark.parametrize("prio", [0, 1])
 @pytest.mark.parametrize("B,nh,N", [(2, 3, 130), (1, 2, 512), (1, 2, 513), (1, 2, 600), (2, 2, 900), (1, 8, 1370), (1, 2, 3571), (1, 2, 3601), (1, 1, 64), (1, 1, 65), (3, 1, 1)])
-def test_attention_ping_pong_kernel_is_bit_identical(H, B, nh, N, prio):
+def test_attention_ping_pong_kernel_is_bit_identical(X, B, nh, N, prio):
     """attn_pp16x_kernel (round 5: 8-wave workgroups, the two waves of a SIMD alternate a matrix phase and a softmax phase, 512 queries share one
     K / V stream) forced with ATTN_KERN = 4 against attn_pp16mq_kernel<2>: the same arithmetic per query, so BIT-identical outputs - across
     sequence lengths that exercise every split of the queries (N < 512: all of them on the attn_pp16mq tail launch; 512 / 513 / 600: full
@@ -112,7 +117,7 @@ def test_attention_ping_pong_kernel_is_bit_identical(H, B, nh, N, prio):
         L.tune("ATTN_KERN", kern)
         L.tune("ATTN_X_PRIO", prio)
         try:
-            outs[kern] = H.attention(1, q, k, v)
+            outs[kern] = X.attention(1, q, k, v)
         finally:
             L.tune("ATTN_KERN", 3)
             L.tune("ATTN_X_PRIO", 0)
@@ -120,13 +125,11 @@ def test_attention_ping_pong_kernel_is_bit_identical(H, B, nh, N, prio):
     assert torch.equal(outs[1], outs[4])
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "moge_amd", "lib", "obj", ".experiments")),
-                    reason="attn_pp16sk_kernel (tools/experiments/) is compiled by `python -m moge_amd.build --experiments` only")
 @pytest.mark.parametrize("qb", [2, 4])
 @pytest.mark.parametrize("B,nh,N,wgs", [(1, 16, 3601, 0),          # the batch-1 shape of the bench: 8 XCD ranges x 96 workgroups, 34.4 tiles each
                                         (1, 8, 1370, 0), (1, 2, 3601, 0), (1, 2, 3601, 5), (2, 3, 130, 1), (2, 3, 130, 4), (2, 3, 130, 17),
                                         (1, 2, 300, 3), (1, 2, 300, 7), (1, 8, 700, 2), (1, 1, 64, 1), (1, 1, 65, 2), (3, 1, 1, 1), (1, 2, 513, 9)])
-def test_attention_stream_k(H, B, nh, N, wgs, qb):
+def test_attention_stream_k(X, B, nh, N, wgs, qb):
     """attn_pp16sk_kernel (round 6 experiment, measured 5-8 us slower at one image and therefore not in the product library): attn_pp16mq's body over equal contiguous ranges of (query block, key tile)
     units; a query block cut into segments is combined by the last-arriving workgroup in segment order.  Forced (ATTN_SK = 2) with partitions that give
     every case - one workgroup walking several whole query blocks (wgs 1), segments of 1-2 tiles (wgs 17 at two tiles per block), three segments per
@@ -145,12 +148,12 @@ def test_attention_stream_k(H, B, nh, N, wgs, qb):
     ref = F.scaled_dot_product_attention(q.cuda(), k.cuda(), v.cuda()).permute(0, 2, 1, 3).reshape(B, N, nh * 64)
     L.tune("ATTN_SK", 0)
     try:
-        plain = H.attention(1, q, k, v)
+        plain = X.attention(1, q, k, v)
         L.tune("ATTN_SK", 2); L.tune("ATTN_SK_QB", qb); L.tune("ATTN_SK_WGS", wgs); L.tune("ATTN_SK_MIN_TILES", 1 if wgs == 0 and N < 2000 else 12)
-        a = H.attention(1, q, k, v)
-        b = H.attention(1, q, k, v)
+        a = X.attention(1, q, k, v)
+        b = X.attention(1, q, k, v)
         L.tune("ATTN_SK_TWICE", 1)
-        c = H.attention(1, q, k, v)
+        c = X.attention(1, q, k, v)
     finally:
         for key, dflt in (("ATTN_SK", 0), ("ATTN_SK_QB", 2), ("ATTN_SK_WGS", 0), ("ATTN_SK_MIN_TILES", 12), ("ATTN_SK_TWICE", 0)):
             L.tune(key, dflt)

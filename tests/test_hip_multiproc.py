@@ -118,11 +118,12 @@ def test_rccl_broadcast_paths_run_on_the_gpu_world1(tmp_path):
     assert got["backend"] == "nccl" and got["ranks"] == 1 and got["blob_unchanged"] and got["same"], got
 
 
-def test_eight_worker_processes_start_and_feed_one_gpu(tmp_path):
-    """`bench.py --gpus 8` as the driver launches it (torch.distributed.run, one rank per process), with all eight ranks on the ONE GPU of
+def test_four_worker_processes_start_and_feed_one_gpu(tmp_path):
+    """`bench.py --gpus 4` as the driver launches it (torch.distributed.run, one rank per process), with all four ranks on the ONE GPU of
     the test box (--single-device, gloo transport: RCCL refuses ranks that share a device) and a tiny model: the N-process path - rendezvous,
-    rank 0's checkpoint load, the blob broadcast to seven config-only ranks, per-rank packing, warm-up, the barrier-bracketed timed region,
-    the max-over-ranks reduction, rank 0's JSON line - runs end to end, and start-up does not serialise across ranks."""
+    rank 0's checkpoint load, the blob broadcast to three config-only ranks, per-rank packing, warm-up, the barrier-bracketed timed region,
+    the max-over-ranks reduction, rank 0's JSON line - runs end to end, and start-up does not serialise across ranks.  Four ranks, not eight:
+    with this process (which already holds the GPU) and the launcher, at most six processes have the device open at once."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     import json
@@ -152,13 +153,13 @@ def test_eight_worker_processes_start_and_feed_one_gpu(tmp_path):
 
     # No retry: round 4 saw ONE unexplained loss of rank 1 in ~15 launches, with the rank's message hidden behind the launcher's
     # summary.  The launch now keeps every rank's output and takes its port from the launcher; if it fails again the log says why.
-    d, w8 = run(8)
-    print("[8 processes, 1 GPU]", json.dumps({k: d[k] for k in ("value", "n_gpus", "ms_per_step", "rccl")}), f"wall {w8:.1f} s")
-    assert d["n_gpus"] == 8 and d["rccl"]["rccl_ranks"] == 8 and d["rccl"]["backend"] == "gloo" and d["rccl"]["single_device"]
-    assert d["config"]["global_batch"] == 32 and d["value"] > 0
-    # eight ranks start concurrently: the slowest rank's start-up (import + rendezvous + load / broadcast + packing + warm-up) stays far below
-    # eight sequential start-ups (one is ~10-20 s, dominated by `import torch` on a cold box)
+    d, w4 = run(4)
+    print("[4 processes, 1 GPU]", json.dumps({k: d[k] for k in ("value", "n_gpus", "ms_per_step", "rccl")}), f"wall {w4:.1f} s")
+    assert d["n_gpus"] == 4 and d["rccl"]["rccl_ranks"] == 4 and d["rccl"]["backend"] == "gloo" and d["rccl"]["single_device"]
+    assert d["config"]["global_batch"] == 16 and d["value"] > 0
+    # four ranks start concurrently: the slowest rank's start-up (import + rendezvous + load / broadcast + packing + warm-up; one is ~10-20 s,
+    # dominated by `import torch` on a cold box) stays bounded, and the per-rank spread below shows no rank waits for another
     assert d["rccl"]["startup_seconds_max_over_ranks"] < 120, d["rccl"]
     per_rank = d["rccl"]["startup_seconds_per_rank"]
-    print("[8 processes, 1 GPU] start-up seconds per rank:", per_rank)
-    assert len(per_rank) == 8 and max(per_rank) < 2.5 * min(per_rank) + 10, per_rank          # no rank waits for another's start-up
+    print("[4 processes, 1 GPU] start-up seconds per rank:", per_rank)
+    assert len(per_rank) == 4 and max(per_rank) < 2.5 * min(per_rank) + 10, per_rank          # no rank waits for another's start-up
