@@ -354,6 +354,37 @@ int moge_align_select(const float* loss, const int32_t* row_batch, int rows, int
 /* alignment.py:399-415: per row the least-squares (a, b) of sqrt(w) x a + b ~ sqrt(w) y; w may be NULL (all ones); x, y, w are (rows, n) */
 int moge_align_lstsq(const float* x, const float* y, const float* w, int rows, int n, float* a, float* b, void* stream);
 
+/* ---- evaluation metrics (reference: moge/test/metrics.py; python mirror moge_amd/metrics.py) ----------------------
+ * Stateless (no handle); every pointer is device memory; results are written asynchronously on `stream`.  Bad sizes -> MOGE_ERR_INVALID.
+ * Sums are float64 from a fixed-order two-stage reduction (`partials` is caller workspace): two calls give the same bits. */
+#define MOGE_METRICS_PARTIALS 256          /* workgroups of the two-stage reductions: partials hold MOGE_METRICS_PARTIALS x (entries) values */
+#define MOGE_METRICS_MAX_SEGMENTS 512      /* distinct segment labels per call */
+/* metrics.py:128 utils3d masked_nearest_resize(mask, size=(out_h, out_w), return_index=True), convention in csrc/metrics.hip: mask (H, W) u8 ->
+ * lr_mask (out_h, out_w) u8, lr_index (2, out_h, out_w) int32 = (rows, cols) */
+int moge_metrics_lr_sample(const uint8_t* mask, int H, int W, int out_h, int out_w, uint8_t* lr_mask, int32_t* lr_index, void* stream);
+/* metrics.py:25-48 for K <= 8 variants of one prediction: pred / gt (n, dim) fp32, dim 1 (depth) or 3 (points), mask (n) u8; params (K, 6) fp32 =
+ * (mode, s, t0, t1, t2, c): mode 0 p*s, 1 p*s+t, 2 p+t, 3 (depth) 1/clamp_min(p*s+t0, c).  out (K, 3) f64 = (sum rel, delta1 count, mask count);
+ * partials: MOGE_METRICS_PARTIALS * K * 3 doubles */
+int moge_metrics_error(const float* pred, const float* gt, const uint8_t* mask, int n, int dim, const float* params, int K, double* partials,
+                       double* out, void* stream);
+/* max(x[mask]) (metrics.py:208) -> out[0] (-inf if the mask is empty); partials: MOGE_METRICS_PARTIALS floats */
+int moge_metrics_masked_max(const float* x, const uint8_t* mask, int n, float* partials, float* out, void* stream);
+/* metrics.py:63-92 for radii 1..3 and the ten thresholds: counts (3, 10, 3) int64 = (TP, gt-label, pred-label) over the valid pairs */
+int moge_metrics_boundary(const float* pred, const float* gt, const uint8_t* mask, int H, int W, int64_t* counts, void* stream);
+/* metrics.py:295-303 per segment: seg (H, W) int32 labels, labels (U) sorted unique (segment u = labels[u]); gt (H, W, 3); lr_mask / lr_index
+ * as moge_metrics_lr_sample -> lr_count (U) low-resolution samples, diameter (U) of gt over segment & mask (NaN if empty); bbox: U * 6 ints workspace */
+int moge_metrics_segment_stats(const int32_t* seg, const uint8_t* mask, const float* gt, int H, int W, const uint8_t* lr_mask, const int32_t* lr_index,
+                               int out_h, int out_w, const int32_t* labels, int U, int32_t* bbox, int32_t* lr_count, float* diameter, void* stream);
+/* metrics.py:300-304 for all kept segments at once: row e packs the low-resolution samples of segment kept[e] (row-major order) into
+ * src / tgt (E, n_max, 3) with weight (E, n_max) = 1 / diameter, zero padding with weight 0 */
+int moge_metrics_segment_pack(const int32_t* seg, int W, const uint8_t* lr_mask, const int32_t* lr_index, int out_h, int out_w, const int32_t* labels, int U,
+                              const int32_t* kept, int E, int n_max, const float* pred, const float* gt, const float* diameter, float* src, float* tgt,
+                              float* weight, void* stream);
+/* metrics.py:304-310: pixels of segment kept[e] & mask aligned with scale[e], shift[e] (3) -> out (E, 3) f64 = (sum dist_err / diameter, delta1
+ * count, pixel count); row (U) = kept row of segment u or -1; partials: MOGE_METRICS_PARTIALS * E * 3 doubles */
+int moge_metrics_segment_error(const int32_t* seg, const uint8_t* mask, const float* pred, const float* gt, int n, const int32_t* labels, int U, const int32_t* row,
+                               const int32_t* kept, int E, const float* scale, const float* shift, const float* diameter, double* partials, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,13 @@ def _load(path: str = LIB_PATH, mode: int = C.RTLD_GLOBAL) -> C.CDLL:
         "moge_align_l1_anchored": (C.c_int, [f32p, f32p, f32p, i32, i32, i32, vp, vp, i32, C.c_float, f32p, f32p, vp, vp]),
         "moge_align_select": (C.c_int, [f32p, vp, i32, i32, f32p, vp, vp]),
         "moge_align_lstsq": (C.c_int, [f32p, f32p, f32p, i32, i32, f32p, f32p, vp]),
+        "moge_metrics_lr_sample": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp]),
+        "moge_metrics_error": (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+        "moge_metrics_masked_max": (C.c_int, [vp, vp, i32, vp, vp, vp]),
+        "moge_metrics_boundary": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
+        "moge_metrics_segment_stats": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]),
+        "moge_metrics_segment_pack": (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "moge_metrics_segment_error": (C.c_int, [vp, vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so does not export what the header declares
@@ -165,7 +172,9 @@ EXPORTS = ["moge_abi_version", "moge_last_error", "moge_create", "moge_create_v1
            "moge_postprocess", "moge_depth_edge_mask", "moge_cast_f16", "moge_sync", "moge_profile_enable", "moge_profile_read", "moge_debug_tap", "moge_tune_set", "moge_test_gemm",
            "moge_test_gemm_ex", "moge_test_layernorm", "moge_test_attention", "moge_test_conv3x3", "moge_test_conv_ex", "moge_test_convt2x2", "moge_test_ct3", "moge_test_preprocess",
            "moge_test_resize_bicubic_aa", "moge_test_groupnorm_relu", "moge_test_norm_act", "moge_test_posembed", "moge_test_recover",
-           "moge_align_l1", "moge_align_l1_anchored", "moge_align_select", "moge_align_lstsq"]
+           "moge_align_l1", "moge_align_l1_anchored", "moge_align_select", "moge_align_lstsq",
+           "moge_metrics_lr_sample", "moge_metrics_error", "moge_metrics_masked_max", "moge_metrics_boundary", "moge_metrics_segment_stats",
+           "moge_metrics_segment_pack", "moge_metrics_segment_error"]
 
 
 def check(code: int) -> None:
