@@ -385,6 +385,38 @@ int moge_metrics_segment_pack(const int32_t* seg, int W, const uint8_t* lr_mask,
 int moge_metrics_segment_error(const int32_t* seg, const uint8_t* mask, const float* pred, const float* gt, int n, const int32_t* labels, int U, const int32_t* row,
                                const int32_t* kept, int E, const float* scale, const float* shift, const float* diameter, double* partials, double* out, void* stream);
 
+/* ---- evaluation data: the per-sample view warp (reference: moge/test/dataloader.py _process_instance; python mirror moge_amd/evaluation.py,
+ * DESIGN.md section 11) -------------------------------------------------------------------------------------------------------------------
+ * Stateless (no handle); every pointer is device memory unless stated; results are written asynchronously on `stream`.  Bad sizes ->
+ * MOGE_ERR_INVALID.  Counts are integer atomics: two calls give the same bits. */
+#define MOGE_EVAL_SEG_BINS 65536           /* segmentation label ids (uint8 / uint16 maps): histogram bins */
+#define MOGE_EVAL_QUANTILE_WORKSPACE 520   /* uint32 workspace of moge_eval_quantile_cut */
+/* workspace of moge_eval_lanczos: tmp_bytes of uint8 intermediate, coeff_ints int32 of coefficient tables (host call, no GPU work) */
+int moge_eval_lanczos_workspace(int H, int W, int out_h, int out_w, int64_t* tmp_bytes, int64_t* coeff_ints);
+/* dataloader.py:145 PIL Image.resize((out_w, out_h), LANCZOS) of src (H, W, 3) u8 -> out (out_h, out_w, 3) u8, bit-exact to Pillow's
+ * Resample.c (the same size is a copy) */
+int moge_eval_lanczos(const uint8_t* src, int H, int W, int out_h, int out_w, uint8_t* tmp, int32_t* coeffs, uint8_t* out, void* stream);
+/* dataloader.py:147-148 masked_nearest_resize(depth (H, W) fp32, mask (H, W) u8) to (out_h, out_w) -> out_depth, out_mask, and
+ * distance = |depth_map_to_point_map(out_depth, K)| with the normalised intrinsics fx, fy, cx, cy */
+int moge_eval_masked_nearest(const float* depth, const uint8_t* mask, int H, int W, int out_h, int out_w, float fx, float fy, float cx, float cy,
+                             float* out_depth, uint8_t* out_mask, float* distance, void* stream);
+/* dataloader.py:149 cv2.resize(INTER_NEAREST) of a (H, W) map of elem_bytes 1 (uint8) or 2 (uint16) */
+int moge_eval_resize_nearest(const void* src, int elem_bytes, int H, int W, int out_h, int out_w, void* dst, void* stream);
+/* dataloader.py:152-164 to the target (out_h, out_w) from the rescaled (h, w) image (u8 RGB), distance, mask (u8) and seg (seg_bytes 1 / 2, or
+ * 0 for none); mats (HOST pointer, 18 floats, read during the call) = transform (3x3) then inv(tgt_intrinsics) (3x3), row-major.  -> out_u8
+ * (out_h, out_w, 3), out_chw (3, out_h, out_w) = out_u8 / 255, out_depth = distance / (ray length + 1e-12), out_mask, out_seg int32 labels and
+ * seg_hist (MOGE_EVAL_SEG_BINS int32) = pixels per label */
+int moge_eval_remap(const uint8_t* image, const float* distance, const uint8_t* mask, const void* seg, int seg_bytes, int h, int w, int out_h, int out_w,
+                    const float* mats, uint8_t* out_u8, float* out_chw, float* out_depth, uint8_t* out_mask, int32_t* out_seg, int32_t* seg_hist, void* stream);
+/* dataloader.py:167-172 in place on depth / mask (n pixels): max_depth = np.nanquantile(where(mask, depth, nan), q) * drop_max_depth
+ * (exact, radix select), mask &= depth <= max_depth, depth = nan_to_num(depth) (* depth_unit if has_unit); count (1 int32) = pixels left in
+ * the mask.  workspace: MOGE_EVAL_QUANTILE_WORKSPACE uint32, max_depth's float bits at workspace[5] */
+int moge_eval_quantile_cut(float* depth, uint8_t* mask, int n, float q, float drop_max_depth, float depth_unit, int has_unit, uint32_t* workspace,
+                           int32_t* count, void* stream);
+/* dataloader.py:173-180: if *count == 0, depth and mask become all ones; points (out_h, out_w, 3) = [u, v, 1] kinv^T * depth with kinv
+ * (HOST pointer, 9 floats) = inv(tgt_intrinsics) */
+int moge_eval_unproject(float* depth, uint8_t* mask, int out_h, int out_w, const float* kinv, const int32_t* count, float* points, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

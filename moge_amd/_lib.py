@@ -146,6 +146,13 @@ def _load(path: str = LIB_PATH, mode: int = C.RTLD_GLOBAL) -> C.CDLL:
         "moge_metrics_segment_stats": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]),
         "moge_metrics_segment_pack": (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "moge_metrics_segment_error": (C.c_int, [vp, vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "moge_eval_lanczos_workspace": (C.c_int, [i32, i32, i32, i32, vp, vp]),
+        "moge_eval_lanczos": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "moge_eval_masked_nearest": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp]),
+        "moge_eval_resize_nearest": (C.c_int, [vp, i32, i32, i32, i32, i32, vp, vp]),
+        "moge_eval_remap": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp]),
+        "moge_eval_quantile_cut": (C.c_int, [vp, vp, i32, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp]),
+        "moge_eval_unproject": (C.c_int, [vp, vp, i32, i32, f32p, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so does not export what the header declares
@@ -174,7 +181,9 @@ EXPORTS = ["moge_abi_version", "moge_last_error", "moge_create", "moge_create_v1
            "moge_test_resize_bicubic_aa", "moge_test_groupnorm_relu", "moge_test_norm_act", "moge_test_posembed", "moge_test_recover",
            "moge_align_l1", "moge_align_l1_anchored", "moge_align_select", "moge_align_lstsq",
            "moge_metrics_lr_sample", "moge_metrics_error", "moge_metrics_masked_max", "moge_metrics_boundary", "moge_metrics_segment_stats",
-           "moge_metrics_segment_pack", "moge_metrics_segment_error"]
+           "moge_metrics_segment_pack", "moge_metrics_segment_error",
+           "moge_eval_lanczos_workspace", "moge_eval_lanczos", "moge_eval_masked_nearest", "moge_eval_resize_nearest", "moge_eval_remap",
+           "moge_eval_quantile_cut", "moge_eval_unproject"]
 
 
 def check(code: int) -> None:

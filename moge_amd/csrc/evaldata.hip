@@ -1,0 +1,472 @@
+// Per-sample view warp of the evaluation data loader (reference moge/test/dataloader.py `_process_instance`, :108-189; python mirror
+// moge_amd/evaluation.py).  Stateless kernels on the caller's stream; every pointer is device memory unless stated.
+// HBM- and gather-bound: no MFMA anywhere in this file.
+//
+//   lanczos          :145  PIL Image.resize(LANCZOS) of the uint8 RGB photo, bit-exact to Pillow's Resample.c (two separable fixed-point passes)
+//   masked nearest   :147-148  utils3d masked_nearest_resize of depth + mask, fused with depth -> distance (norm of the unprojected point)
+//   resize nearest   :149  cv2.resize(INTER_NEAREST) of the uint8 / uint16 segmentation
+//   remap            :153-164  the homography per target pixel, bilinear image, nearest distance / mask / segmentation, ray length, depth,
+//                          and the segment-size histogram (np.unique counts, :187)
+//   quantile cut     :167-178  exact np.nanquantile(depth[mask], 0.01) by a radix select over the float bits, then the mask / nan_to_num / unit
+//   unproject        :173-180  the empty-mask fallback and the points
+//
+// fp32 arithmetic follows the reference's numpy operation order with NO contraction (the pragma below); Pillow's coefficients are float64
+// like its C code.  Counts use integer atomics and nothing sums floats across threads: two runs give the same bits.
+#include "common.h"
+#include "../../include/moge_hip.h"
+
+#pragma clang fp contract(off)
+
+constexpr int EV_THREADS = 256;
+constexpr int EV_BLOCKS = 512;                  // grid of the grid-stride passes of the quantile
+constexpr int PRECISION_BITS = 32 - 8 - 2;      // Pillow Resample.c
+constexpr int EV_SEG_BINS = MOGE_EVAL_SEG_BINS;
+
+static int ev_launched(const char* what) {
+    if (hipGetLastError() != hipSuccess) { moge_internal_set_error(what); return MOGE_ERR_HIP; }
+    return 0;
+}
+
+static inline unsigned ev_grid(long long n) { return (unsigned)((n + EV_THREADS - 1) / EV_THREADS); }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Lanczos (Pillow Resample.c).  precompute_coeffs: scale = in / out, filterscale = max(scale, 1), support = 3 filterscale,
+// ksize = 2 ceil(support) + 1; per output index the window [xmin, xmin + xmax) with xmin = (int)(center - support + 0.5) >= 0,
+// xmax = min((int)(center + support + 0.5), in) - xmin, weights lanczos((x + xmin - center + 0.5) / filterscale) normalised by their
+// sum, then rounded half away from zero to 22-bit fixed point (normalize_coeffs_8bpc).  A pass accumulates 1 << 21 + sum(u8 * k) in int32
+// and clips (v >> 22) to [0, 255].  Horizontal first, over the source rows the vertical pass reads; vertical on that uint8 intermediate.
+// ------------------------------------------------------------------------------------------------------------------------
+static double lz_scale(int in, int out) { return (double)(float)in / out; }      // (in1 - in0) / outSize with a float box
+static int lz_ksize(int in, int out) {
+    const double s = lz_scale(in, out), fs = s < 1.0 ? 1.0 : s;
+    return (int)ceil(3.0 * fs) * 2 + 1;
+}
+
+__device__ __forceinline__ double lz_sinc(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return sin(x) / x;
+}
+__device__ __forceinline__ double lz_filter(double x) { return (-3.0 <= x && x < 3.0) ? lz_sinc(x) * lz_sinc(x / 3) : 0.0; }
+
+__global__ __launch_bounds__(EV_THREADS) void lz_coeff_kernel(int in_size, int out_size, int ksize, int32_t* bounds, int32_t* kk) {
+    const int xx = blockIdx.x * EV_THREADS + threadIdx.x;
+    if (xx >= out_size) return;
+    const double scale = (double)(float)in_size / out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = 3.0 * filterscale;
+    const double center = 0.0 + (xx + 0.5) * scale;
+    const double ss = 1.0 / filterscale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in_size) xmax = in_size;
+    xmax -= xmin;
+    if (xmax > ksize) xmax = ksize;                // never taken (xmax <= 2 support + 1); keeps the table in bounds
+    double ww = 0.0;
+    for (int x = 0; x < xmax; x++) ww += lz_filter((x + xmin - center + 0.5) * ss);
+    int32_t* k = kk + (size_t)xx * ksize;
+    for (int x = 0; x < ksize; x++) {
+        double w = 0.0;
+        if (x < xmax) {
+            w = lz_filter((x + xmin - center + 0.5) * ss);
+            if (ww != 0.0) w /= ww;
+        }
+        k[x] = w < 0 ? (int)(-0.5 + w * (1 << PRECISION_BITS)) : (int)(0.5 + w * (1 << PRECISION_BITS));
+    }
+    bounds[2 * xx] = xmin;
+    bounds[2 * xx + 1] = xmax;
+}
+
+__device__ __forceinline__ uint8_t lz_clip8(int v) {
+    v >>= PRECISION_BITS;
+    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// out (rows, OW, 3) from in rows [row0, row0 + rows) of (., W, 3)
+__global__ __launch_bounds__(EV_THREADS) void lz_horizontal_kernel(const uint8_t* in, int W, int row0, int rows, int OW, int ksize,
+                                                                   const int32_t* bounds, const int32_t* kk, uint8_t* out) {
+    const long long o = (long long)blockIdx.x * EV_THREADS + threadIdx.x;
+    if (o >= (long long)rows * OW) return;
+    const int r = (int)(o / OW), xx = (int)(o - (long long)r * OW);
+    const int xmin = bounds[2 * xx], xmax = bounds[2 * xx + 1];
+    const int32_t* k = kk + (size_t)xx * ksize;
+    const uint8_t* src = in + ((size_t)(r + row0) * W + xmin) * 3;
+    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int x = 0; x < xmax; x++) {
+        s0 += src[3 * x] * k[x];
+        s1 += src[3 * x + 1] * k[x];
+        s2 += src[3 * x + 2] * k[x];
+    }
+    uint8_t* d = out + (size_t)o * 3;
+    d[0] = lz_clip8(s0); d[1] = lz_clip8(s1); d[2] = lz_clip8(s2);
+}
+
+// out (OH, W, 3) from in (., W, 3); bounds are relative to in's first row
+__global__ __launch_bounds__(EV_THREADS) void lz_vertical_kernel(const uint8_t* in, int W, int OH, int ksize, const int32_t* bounds, int row_shift,
+                                                                 const int32_t* kk, uint8_t* out) {
+    const long long o = (long long)blockIdx.x * EV_THREADS + threadIdx.x;
+    if (o >= (long long)OH * W) return;
+    const int yy = (int)(o / W), xx = (int)(o - (long long)yy * W);
+    const int ymin = bounds[2 * yy] - row_shift, ymax = bounds[2 * yy + 1];
+    const int32_t* k = kk + (size_t)yy * ksize;
+    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int y = 0; y < ymax; y++) {
+        const uint8_t* p = in + ((size_t)(y + ymin) * W + xx) * 3;
+        s0 += p[0] * k[y];
+        s1 += p[1] * k[y];
+        s2 += p[2] * k[y];
+    }
+    uint8_t* d = out + (size_t)o * 3;
+    d[0] = lz_clip8(s0); d[1] = lz_clip8(s1); d[2] = lz_clip8(s2);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// masked nearest resize (utils3d stand-in; the convention of csrc/metrics.hip lr_sample_kernel at any size): output cell (i, j) has centre
+// ((i + 0.5) H / OH, (j + 0.5) W / OW) in source pixels and a window of ceil(f) x ceil(f) pixels, f = max(1, H / OH) (resp. W), starting at
+// rint(centre - f / 2); it takes the valid pixel whose centre is nearest the cell centre, first in row-major window order on a tie; without a
+// valid pixel the cell is invalid and takes the nearest in-image pixel.  Float64.  Fused: distance = |(x, y, depth)| with
+// x = (u - cx) / fx * depth, u = (j + 0.5) / OW in fp32 (depth_map_to_point_map) and the norm sqrt((x x + y y) + z z) of numpy's norm3d.
+// ------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(EV_THREADS) void masked_nearest_kernel(const float* depth, const uint8_t* mask, int H, int W, int OH, int OW, float fx,
+                                                                    float fy, float cx, float cy, float* out_depth, uint8_t* out_mask, float* distance) {
+    const long long o = (long long)blockIdx.x * EV_THREADS + threadIdx.x;
+    if (o >= (long long)OH * OW) return;
+    const int i = (int)(o / OW), j = (int)(o - (long long)i * OW);
+    const double fh = fmax(1.0, (double)H / OH), fw = fmax(1.0, (double)W / OW);
+    const double cyc = (i + 0.5) * H / OH, cxc = (j + 0.5) * W / OW;
+    const int wh = (int)ceil(fh), ww = (int)ceil(fw);
+    const int y0 = (int)rint(cyc - fh / 2), x0 = (int)rint(cxc - fw / 2);
+    double best_v = 1e300, best_a = 1e300;
+    int by = -1, bx = -1, ay = min(max(y0, 0), H - 1), ax = min(max(x0, 0), W - 1);
+    for (int dy = 0; dy < wh; dy++) {
+        const int y = y0 + dy;
+        if (y < 0 || y >= H) continue;
+        const double ey = y + 0.5 - cyc;
+        for (int dx = 0; dx < ww; dx++) {
+            const int x = x0 + dx;
+            if (x < 0 || x >= W) continue;
+            const double ex = x + 0.5 - cxc, d = ey * ey + ex * ex;
+            if (d < best_a) { best_a = d; ay = y; ax = x; }
+            if (mask[(size_t)y * W + x] && d < best_v) { best_v = d; by = y; bx = x; }
+        }
+    }
+    const bool valid = by >= 0;
+    const float z = depth[valid ? (size_t)by * W + bx : (size_t)ay * W + ax];
+    const float u = ((float)j + 0.5f) / (float)OW, v = ((float)i + 0.5f) / (float)OH;
+    const float px = (u - cx) / fx * z, py = (v - cy) / fy * z;
+    out_depth[o] = z;
+    out_mask[o] = valid ? 1 : 0;
+    distance[o] = sqrtf(px * px + py * py + z * z);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// cv2.resize(INTER_NEAREST): source index floor(d * (1 / (OW / W))) clamped to W - 1 (resizeNN), the same in y.  `bytes` 1 or 2.
+// ------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(EV_THREADS) void resize_nearest_kernel(const void* src, int bytes, int H, int W, int OH, int OW, void* dst) {
+    const long long o = (long long)blockIdx.x * EV_THREADS + threadIdx.x;
+    if (o >= (long long)OH * OW) return;
+    const int i = (int)(o / OW), j = (int)(o - (long long)i * OW);
+    const double ifx = 1.0 / ((double)OW / W), ify = 1.0 / ((double)OH / H);
+    const int sx = min((int)floor(j * ifx), W - 1), sy = min((int)floor(i * ify), H - 1);
+    const size_t s = (size_t)sy * W + sx;
+    if (bytes == 1) static_cast<uint8_t*>(dst)[o] = static_cast<const uint8_t*>(src)[s];
+    else static_cast<uint16_t*>(dst)[o] = static_cast<const uint16_t*>(src)[s];
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// remap.  Per target pixel (y, x) of (OH, OW): uv = ((x + 0.5) / OW, (y + 0.5) / OH); p = [u, v, 1] T^T; uv' = p.xy / (p.z + 1e-12);
+// pixel = uv' * (w, h) - 0.5 in the rescaled source (h, w).  Border constant 0.  Image: bilinear with float weights fx = x - floor(x)
+// ((a (1 - fx) + b fx) (1 - fy) + (c (1 - fx) + d fx) fy, then rint and clip); distance / mask / segmentation: nearest at rint (half to even).
+// Ray length |[u, v, 1] Kinv^T| (sqrt((x x + y y) + z z)); depth = distance / (ray + 1e-12).  The segmentation label histogram is counted
+// here (integer atomics).
+// ------------------------------------------------------------------------------------------------------------------------
+struct EvMats { float T[9]; float Ki[9]; };
+
+__global__ __launch_bounds__(EV_THREADS) void remap_kernel(const uint8_t* image, const float* distance, const uint8_t* mask, const void* seg, int seg_bytes,
+                                                           int h, int w, int OH, int OW, EvMats m, uint8_t* out_u8, float* out_chw, float* out_depth,
+                                                           uint8_t* out_mask, int32_t* out_seg, int32_t* hist) {
+    const long long o = (long long)blockIdx.x * EV_THREADS + threadIdx.x;
+    if (o >= (long long)OH * OW) return;
+    const int y = (int)(o / OW), x = (int)(o - (long long)y * OW);
+    const float u = ((float)x + 0.5f) / (float)OW, v = ((float)y + 0.5f) / (float)OH;
+    const float p0 = u * m.T[0] + v * m.T[1] + m.T[2];
+    const float p1 = u * m.T[3] + v * m.T[4] + m.T[5];
+    const float p2 = u * m.T[6] + v * m.T[7] + m.T[8];
+    const float den = p2 + 1e-12f;
+    const float px = p0 / den * (float)w - 0.5f, py = p1 / den * (float)h - 0.5f;
+
+    // bilinear, constant border (a tap outside the image contributes 0)
+    float acc[3] = {0.f, 0.f, 0.f};
+    if (px > -2.f && px < (float)w + 1.f && py > -2.f && py < (float)h + 1.f) {
+        const float flx = floorf(px), fly = floorf(py);
+        const int x0 = (int)flx, y0 = (int)fly;
+        const float fx = px - flx, fy = py - fly;
+        for (int c = 0; c < 3; c++) {
+            float t[4];
+            for (int q = 0; q < 4; q++) {
+                const int xx = x0 + (q & 1), yy = y0 + (q >> 1);
+                t[q] = (xx >= 0 && xx < w && yy >= 0 && yy < h) ? (float)image[((size_t)yy * w + xx) * 3 + c] : 0.f;
+            }
+            acc[c] = (t[0] * (1.f - fx) + t[1] * fx) * (1.f - fy) + (t[2] * (1.f - fx) + t[3] * fx) * fy;
+        }
+    }
+    for (int c = 0; c < 3; c++) {
+        const float r = rintf(acc[c]);
+        const uint8_t b = (uint8_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r));
+        out_u8[(size_t)o * 3 + c] = b;
+        out_chw[(size_t)c * OH * OW + o] = (float)b / 255.f;
+    }
+
+    // nearest, constant border
+    const float rx = rintf(px), ry = rintf(py);
+    const bool inside = rx >= 0.f && rx <= (float)(w - 1) && ry >= 0.f && ry <= (float)(h - 1);
+    const size_t s = inside ? (size_t)ry * w + (size_t)rx : 0;
+    const float dist = inside ? distance[s] : 0.f;
+    out_mask[o] = (inside && mask[s] > 0) ? 1 : 0;
+    if (seg_bytes) {
+        const int label = inside ? (seg_bytes == 1 ? (int)static_cast<const uint8_t*>(seg)[s] : (int)static_cast<const uint16_t*>(seg)[s]) : 0;
+        out_seg[o] = label;
+        atomicAdd(&hist[label], 1);
+    }
+
+    const float a = u * m.Ki[0] + v * m.Ki[1] + m.Ki[2];
+    const float b = u * m.Ki[3] + v * m.Ki[4] + m.Ki[5];
+    const float c = u * m.Ki[6] + v * m.Ki[7] + m.Ki[8];
+    const float ray = sqrtf(a * a + b * b + c * c);
+    out_depth[o] = dist / (ray + 1e-12f);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// quantile cut.  np.nanquantile(where(mask, depth, nan), q) for float32 (numpy 2.2, method 'linear', all in float32):
+//   n valid values; vi = n q + (1 + q (-1)) - 1; prev = floor(vi), next = prev + 1; vi >= n - 1 -> prev = next = n - 1 (gamma = vi + 1);
+//   gamma = vi - prev; a, b = the prev-th / next-th smallest; _lerp: d = b - a; r = a + d gamma, or b - d (1 - gamma) when gamma >= 0.5.
+// The two order statistics come from a radix select over the order-preserving bit pattern of the valid values: four 8-bit digit passes,
+// each a histogram over all pixels (integer atomics) and one single-thread scan.  No sort.  Then max_depth = r * drop_max_depth, and per
+// pixel (:168-172): mask &= depth <= max_depth, depth = nan_to_num(depth), depth *= unit; the surviving mask pixels are counted.
+// state: [0] n, [1..2] rank left, [3..4] key prefix, [5] float bits of max_depth.
+// ------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t f2key(float f) {
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+__global__ __launch_bounds__(EV_THREADS) void q_hist_kernel(const float* depth, const uint8_t* mask, int n, int pass, const uint32_t* state, uint32_t* hist) {
+    __shared__ uint32_t h[2][256];
+    for (int t = threadIdx.x; t < 512; t += EV_THREADS) h[t >> 8][t & 255] = 0;
+    __syncthreads();
+    const int shift = 24 - 8 * pass;
+    const uint32_t p0 = pass ? state[3] : 0, p1 = pass ? state[4] : 0;
+    for (int i = blockIdx.x * EV_THREADS + threadIdx.x; i < n; i += EV_BLOCKS * EV_THREADS) {
+        const float d = depth[i];
+        if (!mask[i] || d != d) continue;
+        const uint32_t k = f2key(d);
+        const uint32_t high = pass ? (k >> (shift + 8)) : 0u, digit = (k >> shift) & 255u;
+        if (high == p0) atomicAdd(&h[0][digit], 1u);
+        if (pass && high == p1) atomicAdd(&h[1][digit], 1u);
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < 512; t += EV_THREADS)
+        if (h[t >> 8][t & 255]) atomicAdd(&hist[t], h[t >> 8][t & 255]);
+}
+
+__global__ void q_select_kernel(int pass, float q, float drop, uint32_t* state, uint32_t* hist) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (pass == 0) {
+        uint32_t n = 0;
+        for (int b = 0; b < 256; b++) n += hist[b];
+        state[0] = n;
+        if (n == 0) { state[1] = state[2] = 0; }
+        else {
+            const float vi = (float)n * q + (1.f + q * -1.f) - 1.f;
+            const bool above = vi >= (float)(n - 1);
+            const uint32_t prev = above ? n - 1 : (uint32_t)floorf(vi);
+            state[1] = prev;
+            state[2] = above ? n - 1 : prev + 1;
+        }
+        for (int b = 0; b < 256; b++) hist[256 + b] = hist[b];       // both selections start from the same histogram
+    }
+    for (int s = 0; s < 2; s++) {
+        uint32_t rank = state[1 + s], digit = 0, below = 0;
+        for (; digit < 255; digit++) {
+            const uint32_t c = hist[256 * s + digit];
+            if (below + c > rank) break;
+            below += c;
+        }
+        state[1 + s] = rank - below;
+        state[3 + s] = (state[3 + s] << 8) | digit;
+    }
+    for (int b = 0; b < 512; b++) hist[b] = 0;
+    if (pass == 3) {
+        const uint32_t n = state[0];
+        float r = __builtin_nanf("");
+        if (n) {
+            const float vi = (float)n * q + (1.f + q * -1.f) - 1.f;
+            const bool above = vi >= (float)(n - 1);
+            const double prev = above ? -1.0 : (double)floorf(vi);          // numpy stores index -1 for "last" and takes gamma from it
+            const float gamma = (float)((double)vi - prev);
+            const float a = key2f(state[3]), b = key2f(state[4]);
+            const float d = b - a;
+            r = gamma >= 0.5f ? b - d * (1.f - gamma) : a + d * gamma;
+        }
+        const float md = r * drop;
+        state[5] = __float_as_uint(md);
+    }
+}
+
+__global__ __launch_bounds__(EV_THREADS) void q_apply_kernel(float* depth, uint8_t* mask, int n, const uint32_t* state, float unit, int has_unit, int32_t* count) {
+    __shared__ int32_t part[EV_THREADS / 64];
+    const float md = __uint_as_float(state[5]);
+    int32_t c = 0;
+    for (int i = blockIdx.x * EV_THREADS + threadIdx.x; i < n; i += EV_BLOCKS * EV_THREADS) {
+        float d = depth[i];
+        const bool m = mask[i] && d <= md;
+        mask[i] = m ? 1 : 0;
+        c += m;
+        d = d != d ? 0.f : (d == __builtin_inff() ? 3.40282347e38f : (d == -__builtin_inff() ? -3.40282347e38f : d));
+        if (has_unit) d = d * unit;
+        depth[i] = d;
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t s = 0;
+        for (int k = 0; k < EV_THREADS / 64; k++) s += part[k];
+        if (s) atomicAdd(count, s);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// unproject (:173-180): an empty mask turns into all ones (mask and depth); points = [u, v, 1] Kinv^T * depth.
+// ------------------------------------------------------------------------------------------------------------------------
+struct EvKinv { float Ki[9]; };
+
+__global__ __launch_bounds__(EV_THREADS) void unproject_kernel(float* depth, uint8_t* mask, int OH, int OW, EvKinv m, const int32_t* count, float* points) {
+    const long long o = (long long)blockIdx.x * EV_THREADS + threadIdx.x;
+    if (o >= (long long)OH * OW) return;
+    const int y = (int)(o / OW), x = (int)(o - (long long)y * OW);
+    float d = depth[o];
+    if (*count == 0) { d = 1.f; depth[o] = 1.f; mask[o] = 1; }
+    const float u = ((float)x + 0.5f) / (float)OW, v = ((float)y + 0.5f) / (float)OH;
+    points[3 * o] = (u * m.Ki[0] + v * m.Ki[1] + m.Ki[2]) * d;
+    points[3 * o + 1] = (u * m.Ki[3] + v * m.Ki[4] + m.Ki[5]) * d;
+    points[3 * o + 2] = (u * m.Ki[6] + v * m.Ki[7] + m.Ki[8]) * d;
+}
+
+extern "C" {
+
+int moge_eval_lanczos_workspace(int H, int W, int out_h, int out_w, int64_t* tmp_bytes, int64_t* coeff_ints) {
+    if (!tmp_bytes || !coeff_ints || H < 1 || W < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_lanczos_workspace: bad argument"); return MOGE_ERR_INVALID; }
+    *tmp_bytes = (int64_t)H * out_w * 3;
+    *coeff_ints = (int64_t)out_w * (2 + lz_ksize(W, out_w)) + (int64_t)out_h * (2 + lz_ksize(H, out_h));
+    return 0;
+}
+
+int moge_eval_lanczos(const uint8_t* src, int H, int W, int out_h, int out_w, uint8_t* tmp, int32_t* coeffs, uint8_t* out, void* stream) {
+    if (!src || !out || !tmp || !coeffs) { moge_internal_set_error("moge_eval_lanczos: null argument"); return MOGE_ERR_INVALID; }
+    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_lanczos: empty image"); return MOGE_ERR_INVALID; }
+    hipStream_t st = (hipStream_t)stream;
+    if (H == out_h && W == out_w) {                     // Image.resize returns a copy when the size is unchanged
+        if (hipMemcpyAsync(out, src, (size_t)H * W * 3, hipMemcpyDeviceToDevice, st) != hipSuccess) { moge_internal_set_error("moge_eval_lanczos: copy failed"); return MOGE_ERR_HIP; }
+        return 0;
+    }
+    const int kh = lz_ksize(W, out_w), kv = lz_ksize(H, out_h);
+    int32_t* bh = coeffs;
+    int32_t* kkh = bh + 2 * (size_t)out_w;
+    int32_t* bv = kkh + (size_t)out_w * kh;
+    int32_t* kkv = bv + 2 * (size_t)out_h;
+    const bool need_h = W != out_w, need_v = H != out_h;
+    hipLaunchKernelGGL(lz_coeff_kernel, dim3(ev_grid(out_w)), dim3(EV_THREADS), 0, st, W, out_w, kh, bh, kkh);
+    if (int rc = ev_launched("moge_eval_lanczos: coefficient launch failed")) return rc;
+    hipLaunchKernelGGL(lz_coeff_kernel, dim3(ev_grid(out_h)), dim3(EV_THREADS), 0, st, H, out_h, kv, bv, kkv);
+    if (int rc = ev_launched("moge_eval_lanczos: coefficient launch failed")) return rc;
+    // rows the vertical pass reads: [first, last) from the host-side copy of the same bounds arithmetic
+    int first = 0, last = H;
+    if (need_v) {
+        const double s = lz_scale(H, out_h), fs = s < 1.0 ? 1.0 : s, support = 3.0 * fs;
+        first = (int)(0.0 + 0.5 * s - support + 0.5);
+        if (first < 0) first = 0;
+        const double c = (out_h - 1 + 0.5) * s;
+        int xmin = (int)(c - support + 0.5), xmax = (int)(c + support + 0.5);
+        if (xmin < 0) xmin = 0;
+        if (xmax > H) xmax = H;
+        last = xmin + (xmax - xmin);
+    }
+    if (need_h) {
+        const int rows = last - first;
+        uint8_t* dst = need_v ? tmp : out;
+        hipLaunchKernelGGL(lz_horizontal_kernel, dim3(ev_grid((long long)rows * out_w)), dim3(EV_THREADS), 0, st, src, W, first, rows, out_w, kh, bh, kkh, dst);
+        if (int rc = ev_launched("moge_eval_lanczos: horizontal launch failed")) return rc;
+    }
+    if (need_v) {
+        const uint8_t* vin = need_h ? tmp : src;
+        const int shift = need_h ? first : 0;
+        hipLaunchKernelGGL(lz_vertical_kernel, dim3(ev_grid((long long)out_h * out_w)), dim3(EV_THREADS), 0, st, vin, out_w, out_h, kv, bv, shift, kkv, out);
+        if (int rc = ev_launched("moge_eval_lanczos: vertical launch failed")) return rc;
+    }
+    return 0;
+}
+
+int moge_eval_masked_nearest(const float* depth, const uint8_t* mask, int H, int W, int out_h, int out_w, float fx, float fy, float cx, float cy,
+                             float* out_depth, uint8_t* out_mask, float* distance, void* stream) {
+    if (!depth || !mask || !out_depth || !out_mask || !distance) { moge_internal_set_error("moge_eval_masked_nearest: null argument"); return MOGE_ERR_INVALID; }
+    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_masked_nearest: empty map"); return MOGE_ERR_INVALID; }
+    hipLaunchKernelGGL(masked_nearest_kernel, dim3(ev_grid((long long)out_h * out_w)), dim3(EV_THREADS), 0, (hipStream_t)stream, depth, mask, H, W, out_h,
+                       out_w, fx, fy, cx, cy, out_depth, out_mask, distance);
+    return ev_launched("moge_eval_masked_nearest: launch failed");
+}
+
+int moge_eval_resize_nearest(const void* src, int elem_bytes, int H, int W, int out_h, int out_w, void* dst, void* stream) {
+    if (!src || !dst || (elem_bytes != 1 && elem_bytes != 2)) { moge_internal_set_error("moge_eval_resize_nearest: null argument or element size not 1 / 2"); return MOGE_ERR_INVALID; }
+    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_resize_nearest: empty map"); return MOGE_ERR_INVALID; }
+    hipLaunchKernelGGL(resize_nearest_kernel, dim3(ev_grid((long long)out_h * out_w)), dim3(EV_THREADS), 0, (hipStream_t)stream, src, elem_bytes, H, W,
+                       out_h, out_w, dst);
+    return ev_launched("moge_eval_resize_nearest: launch failed");
+}
+
+int moge_eval_remap(const uint8_t* image, const float* distance, const uint8_t* mask, const void* seg, int seg_bytes, int h, int w, int out_h, int out_w,
+                    const float* mats, uint8_t* out_u8, float* out_chw, float* out_depth, uint8_t* out_mask, int32_t* out_seg, int32_t* seg_hist, void* stream) {
+    if (!image || !distance || !mask || !mats || !out_u8 || !out_chw || !out_depth || !out_mask) { moge_internal_set_error("moge_eval_remap: null argument"); return MOGE_ERR_INVALID; }
+    if (seg_bytes && (!seg || !out_seg || !seg_hist || (seg_bytes != 1 && seg_bytes != 2))) { moge_internal_set_error("moge_eval_remap: segmentation arguments"); return MOGE_ERR_INVALID; }
+    if (h < 1 || w < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_remap: empty map"); return MOGE_ERR_INVALID; }
+    hipStream_t st = (hipStream_t)stream;
+    EvMats m;
+    for (int i = 0; i < 9; i++) { m.T[i] = mats[i]; m.Ki[i] = mats[9 + i]; }
+    if (seg_bytes && hipMemsetAsync(seg_hist, 0, EV_SEG_BINS * sizeof(int32_t), st) != hipSuccess) { moge_internal_set_error("moge_eval_remap: memset failed"); return MOGE_ERR_HIP; }
+    hipLaunchKernelGGL(remap_kernel, dim3(ev_grid((long long)out_h * out_w)), dim3(EV_THREADS), 0, st, image, distance, mask, seg, seg_bytes, h, w, out_h, out_w,
+                       m, out_u8, out_chw, out_depth, out_mask, out_seg, seg_hist);
+    return ev_launched("moge_eval_remap: launch failed");
+}
+
+int moge_eval_quantile_cut(float* depth, uint8_t* mask, int n, float q, float drop_max_depth, float depth_unit, int has_unit, uint32_t* workspace,
+                           int32_t* count, void* stream) {
+    if (!depth || !mask || !workspace || !count || n < 1) { moge_internal_set_error("moge_eval_quantile_cut: null argument or n < 1"); return MOGE_ERR_INVALID; }
+    if (!(q >= 0.f && q <= 1.f)) { moge_internal_set_error("moge_eval_quantile_cut: q outside [0, 1]"); return MOGE_ERR_INVALID; }
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* state = workspace;
+    uint32_t* hist = workspace + 8;
+    if (hipMemsetAsync(workspace, 0, MOGE_EVAL_QUANTILE_WORKSPACE * sizeof(uint32_t), st) != hipSuccess ||
+        hipMemsetAsync(count, 0, sizeof(int32_t), st) != hipSuccess) { moge_internal_set_error("moge_eval_quantile_cut: memset failed"); return MOGE_ERR_HIP; }
+    for (int pass = 0; pass < 4; pass++) {
+        hipLaunchKernelGGL(q_hist_kernel, dim3(EV_BLOCKS), dim3(EV_THREADS), 0, st, depth, mask, n, pass, state, hist);
+        if (int rc = ev_launched("moge_eval_quantile_cut: histogram launch failed")) return rc;
+        hipLaunchKernelGGL(q_select_kernel, dim3(1), dim3(64), 0, st, pass, q, drop_max_depth, state, hist);
+        if (int rc = ev_launched("moge_eval_quantile_cut: select launch failed")) return rc;
+    }
+    hipLaunchKernelGGL(q_apply_kernel, dim3(EV_BLOCKS), dim3(EV_THREADS), 0, st, depth, mask, n, state, depth_unit, has_unit, count);
+    return ev_launched("moge_eval_quantile_cut: apply launch failed");
+}
+
+int moge_eval_unproject(float* depth, uint8_t* mask, int out_h, int out_w, const float* kinv, const int32_t* count, float* points, void* stream) {
+    if (!depth || !mask || !kinv || !count || !points) { moge_internal_set_error("moge_eval_unproject: null argument"); return MOGE_ERR_INVALID; }
+    if (out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_unproject: empty map"); return MOGE_ERR_INVALID; }
+    EvKinv m;
+    for (int i = 0; i < 9; i++) m.Ki[i] = kinv[i];
+    hipLaunchKernelGGL(unproject_kernel, dim3(ev_grid((long long)out_h * out_w)), dim3(EV_THREADS), 0, (hipStream_t)stream, depth, mask, out_h, out_w, m,
+                       count, points);
+    return ev_launched("moge_eval_unproject: launch failed");
+}
+
+}  // extern "C"

@@ -1,12 +1,12 @@
 """`python -m moge_amd.scripts.cli <command>` - the reference's `moge` command group (moge/scripts/cli.py:10-24, pyproject.toml:36) with the
-commands that exist on this path: `infer`, `infer_panorama`, `infer_baseline`.  `app` (Gradio), `eval_baseline` (the metric harness - its
-plugin side is baselines/moge_mi355x.py, its alignment solvers moge_amd.alignment), `train` and `vis_data` are outside the hot path
+commands that exist on this path: `infer`, `infer_panorama`, `infer_baseline` and `eval_baseline` (the benchmark harness: data warp in
+moge_amd.evaluation, metrics in moge_amd.metrics).  `app` (Gradio), `train` and `vis_data` are outside the hot path
  and are run from the reference checkout with the plugin."""
 import importlib
 
 import click
 
-COMMANDS = ("infer", "infer_baseline", "infer_panorama")      # module moge_amd.scripts.<name>, click command `main`
+COMMANDS = ("eval_baseline", "infer", "infer_baseline", "infer_panorama")      # module moge_amd.scripts.<name>, click command `main`
 
 
 class _LazyGroup(click.Group):
