@@ -367,7 +367,7 @@ int moge_metrics_lr_sample(const uint8_t* mask, int H, int W, int out_h, int out
  * partials: MOGE_METRICS_PARTIALS * K * 3 doubles */
 int moge_metrics_error(const float* pred, const float* gt, const uint8_t* mask, int n, int dim, const float* params, int K, double* partials,
                        double* out, void* stream);
-/* max(x[mask]) (metrics.py:208) -> out[0] (-inf if the mask is empty); partials: MOGE_METRICS_PARTIALS floats */
+/* max(x[mask]) (metrics.py:208) -> out[0] (-inf if the mask is empty, NaN if a masked value is NaN, +0 above -0); partials: MOGE_METRICS_PARTIALS floats */
 int moge_metrics_masked_max(const float* x, const uint8_t* mask, int n, float* partials, float* out, void* stream);
 /* metrics.py:63-92 for radii 1..3 and the ten thresholds: counts (3, 10, 3) int64 = (TP, gt-label, pred-label) over the valid pairs */
 int moge_metrics_boundary(const float* pred, const float* gt, const uint8_t* mask, int H, int W, int64_t* counts, void* stream);

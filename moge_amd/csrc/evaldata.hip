@@ -239,7 +239,8 @@ __global__ __launch_bounds__(EV_THREADS) void remap_kernel(const uint8_t* image,
 
 // ------------------------------------------------------------------------------------------------------------------------
 // quantile cut.  np.nanquantile(where(mask, depth, nan), q) for float32 (numpy 2.2, method 'linear', all in float32):
-//   n valid values; vi = n q + (1 + q (-1)) - 1; prev = floor(vi), next = prev + 1; vi >= n - 1 -> prev = next = n - 1 (gamma = vi + 1);
+//   n valid values; vi = (n - 1) q (the 'linear' method's own virtual index, not the general n q + (1 - q) - 1: the fp32 roundings differ);
+//   prev = floor(vi), next = prev + 1; vi >= n - 1 -> prev = next = n - 1 (gamma = vi + 1);
 //   gamma = vi - prev; a, b = the prev-th / next-th smallest; _lerp: d = b - a; r = a + d gamma, or b - d (1 - gamma) when gamma >= 0.5.
 // The two order statistics come from a radix select over the order-preserving bit pattern of the valid values: four 8-bit digit passes,
 // each a histogram over all pixels (integer atomics) and one single-thread scan.  No sort.  Then max_depth = r * drop_max_depth, and per
@@ -279,7 +280,7 @@ __global__ void q_select_kernel(int pass, float q, float drop, uint32_t* state, 
         state[0] = n;
         if (n == 0) { state[1] = state[2] = 0; }
         else {
-            const float vi = (float)n * q + (1.f + q * -1.f) - 1.f;
+            const float vi = (float)(n - 1) * q;
             const bool above = vi >= (float)(n - 1);
             const uint32_t prev = above ? n - 1 : (uint32_t)floorf(vi);
             state[1] = prev;
@@ -302,7 +303,7 @@ __global__ void q_select_kernel(int pass, float q, float drop, uint32_t* state, 
         const uint32_t n = state[0];
         float r = __builtin_nanf("");
         if (n) {
-            const float vi = (float)n * q + (1.f + q * -1.f) - 1.f;
+            const float vi = (float)(n - 1) * q;
             const bool above = vi >= (float)(n - 1);
             const double prev = above ? -1.0 : (double)floorf(vi);          // numpy stores index -1 for "last" and takes gamma from it
             const float gamma = (float)((double)vi - prev);

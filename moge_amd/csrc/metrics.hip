@@ -171,7 +171,7 @@ __global__ __launch_bounds__(MET_THREADS) void masked_max_kernel(const float* x,
     __shared__ int red[MET_WAVES];
     int m = f2ord(-__builtin_inff());
     for (int i = blockIdx.x * MET_THREADS + threadIdx.x; i < n; i += MET_BLOCKS * MET_THREADS)
-        if (mask[i]) m = max(m, f2ord(x[i]));
+        if (mask[i]) { const float v = x[i]; m = max(m, v != v ? 0x7fffffff : f2ord(v)); }     // any NaN (either sign) wins, as in torch.max
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;

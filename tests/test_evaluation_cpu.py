@@ -10,7 +10,8 @@ import pytest
 from PIL import Image
 
 from moge_amd import evaluation as E
-from tests.eval_fixtures import CASES, build_instance, instance_digest, load, recipe
+from tests.eval_fixtures import CASES, build_instance, config, instance_digest, load, recipe
+from tests.eval_reference import lanczos_np
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -103,60 +104,8 @@ def test_select_segments_order_and_cuts():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# Lanczos: the fixed-point convention of csrc/evaldata.hip, restated, against Pillow
+# Lanczos: the fixed-point convention of csrc/evaldata.hip, restated (tests/eval_reference.py), against Pillow
 # ---------------------------------------------------------------------------------------------------------------------------------------
-def _lz_coeffs(in_size, out_size):
-    scale = float(np.float32(in_size)) / out_size
-    fs = max(scale, 1.0)
-    support = 3.0 * fs
-    ksize = int(math.ceil(support)) * 2 + 1
-
-    def filt(x):
-        def sinc(v):
-            if v == 0.0:
-                return 1.0
-            v = v * math.pi
-            return math.sin(v) / v
-        return sinc(x) * sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
-
-    bounds, kk = [], np.zeros((out_size, ksize), np.int64)
-    for xx in range(out_size):
-        center = 0.0 + (xx + 0.5) * scale
-        xmin = max(int(center - support + 0.5), 0)
-        xmax = min(int(center + support + 0.5), in_size) - xmin
-        w = [filt((x + xmin - center + 0.5) / fs) for x in range(xmax)]
-        ww = sum(w)
-        for x in range(xmax):
-            v = w[x] / ww if ww != 0.0 else w[x]
-            kk[xx, x] = int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22))
-        bounds.append((xmin, xmax))
-    return bounds, kk
-
-
-def _lz_pass(src, bounds, kk):
-    """src (N, in, C) uint8 -> (N, out, C) along axis 1"""
-    out = np.zeros((src.shape[0], len(bounds), src.shape[2]), np.uint8)
-    for xx, (xmin, xmax) in enumerate(bounds):
-        acc = (1 << 21) + np.einsum("nkc,k->nc", src[:, xmin:xmin + xmax].astype(np.int64), kk[xx, :xmax])
-        out[:, xx] = np.clip(acc >> 22, 0, 255)
-    return out
-
-
-def lanczos_np(img, h, w):
-    H, W = img.shape[:2]
-    if (H, W) == (h, w):
-        return img.copy()
-    bh, kh = _lz_coeffs(W, w)
-    bv, kv = _lz_coeffs(H, h)
-    first, last = bv[0][0], bv[-1][0] + bv[-1][1]
-    if W != w:
-        img = _lz_pass(img[first:last] if H != h else img, bh, kh)
-        bv = [(a - first, b) for a, b in bv] if H != h else bv
-    if H != h:
-        img = _lz_pass(img.transpose(1, 0, 2), bv, kv).transpose(1, 0, 2)
-    return img
-
-
 @pytest.mark.parametrize("src,dst", [((13, 17), (5, 7)), ((11, 9), (29, 31)), ((23, 7), (7, 23)), ((40, 33), (40, 11)), ((9, 50), (27, 50)),
                                      ((61, 45), (19, 14))])
 def test_lanczos_convention_matches_pillow(src, dst):
@@ -186,7 +135,7 @@ def radix_quantile(depth, mask, q=0.01):
     if n == 0:
         return np.float32(np.nan)
     qf = np.float32(q)
-    vi = np.float32(n) * qf + (np.float32(1) + qf * np.float32(-1)) - np.float32(1)
+    vi = np.float32(n - 1) * qf                        # numpy's 'linear' virtual index
     above = vi >= np.float32(n - 1)
     ranks = [n - 1, n - 1] if above else [int(np.floor(vi)), int(np.floor(vi)) + 1]
     keys = _key(vals)
@@ -214,7 +163,7 @@ def _same(a, b):
     return (np.isnan(a) and np.isnan(b)) or np.float32(a).tobytes() == np.float32(b).tobytes()
 
 
-@pytest.mark.parametrize("case", ["ties", "n1", "n1_inf", "integer_index", "negative", "infs", "random", "empty", "denormal"])
+@pytest.mark.parametrize("case", ["ties", "n1", "n1_inf", "integer_index", "negative", "infs", "random", "empty", "denormal", "n3", "n1000"])
 def test_radix_quantile_matches_numpy(case):
     rng = np.random.default_rng(len(case))
     if case == "ties":
@@ -232,6 +181,8 @@ def test_radix_quantile_matches_numpy(case):
         v = np.concatenate([np.full(3, -np.inf), rng.uniform(1, 2, 50), np.full(4, np.inf)]).astype(np.float32)
     elif case == "denormal":
         v = np.float32([1e-45, 0.0, 2e-45, 1e-40] * 30)
+    elif case in ("n3", "n1000"):                      # (n - 1) q and n q + (1 - q) - 1 round apart in fp32 at q = 0.01 / 0.999
+        v = rng.lognormal(1, 1, int(case[1:])).astype(np.float32)
     elif case == "empty":
         v = np.float32([np.nan, np.nan])
     else:
@@ -240,10 +191,11 @@ def test_radix_quantile_matches_numpy(case):
     if case == "random":
         mask = rng.random(v.shape) > 0.3
         v[rng.random(v.shape) > 0.9] = np.nan
-    with np.errstate(all="ignore"), __import__("warnings").catch_warnings():
-        __import__("warnings").simplefilter("ignore")
-        ref = np.nanquantile(np.where(mask, v, np.nan), 0.01)
-    assert _same(radix_quantile(v, mask), ref), (radix_quantile(v, mask), ref)
+    for q in (0.0, 0.01, 0.5, 0.999, 1.0):
+        with np.errstate(all="ignore"), __import__("warnings").catch_warnings():
+            __import__("warnings").simplefilter("ignore")
+            ref = np.nanquantile(np.where(mask, v, np.nan), q)
+        assert _same(radix_quantile(v, mask, q), ref), (q, radix_quantile(v, mask, q), ref)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -262,3 +214,44 @@ def test_eval_baseline_options():
     assert out.exit_code == 0
     for opt in ("--baseline", "--config", "--output", "--oracle", "--dump_pred", "--dump_gt"):
         assert opt in out.output
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the numpy restatement of remap / quantile cut / unproject (tests/eval_reference.py; what the GPU sweeps compare the kernels with) against
+# the reference's stored results, fed the restated Lanczos (checked by sha256) and the reference's stored masked nearest depth and mask
+# ---------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", CASES)
+def test_remap_reference_matches_fixture(name):
+    import hashlib
+    from tests import eval_reference as R
+    z = load(name)
+    inst = build_instance(recipe(z))
+    cfg = config(z)
+    geo = E.warp_geometry(inst["image"].shape[0], inst["image"].shape[1], inst["intrinsics"], inst["width"], inst["height"])
+    h, w = geo["rescaled_size"]
+    OH, OW = inst["height"], inst["width"]
+    rescaled = lanczos_np(inst["image"], h, w)
+    assert hashlib.sha256(np.ascontiguousarray(rescaled).tobytes()).hexdigest() == str(z["lanczos_sha256"])
+    mnr_depth = z["mnr_depth"]
+    mnr_mask = np.unpackbits(z["mnr_mask"])[: h * w].reshape(h, w)
+    dist = R.distance_ref(mnr_depth, inst["intrinsics"])
+    kinv = np.asarray(geo["tgt_intrinsics_inv"], np.float32)
+    out = R.remap_ref(rescaled, dist, mnr_mask, None, np.asarray(geo["transform"], np.float32), kinv, OH, OW)
+
+    diff = np.abs(out["image"][::2].astype(np.int16) - z["image_rows"].astype(np.int16))
+    assert diff.max() <= 1 and diff.any(axis=-1).mean() <= 1e-3, (diff.max(), diff.any(axis=-1).mean())
+
+    md, mask, depth, count = R.quantile_cut_ref(out["depth"], out["mask"], 0.01, cfg["drop_max_depth"], cfg["depth_unit"])
+    assert R.same_bits(md, z["max_depth"]), (md, z["max_depth"])
+    mask, depth = mask.reshape(OH, OW), depth.reshape(OH, OW)
+    knife = np.unpackbits(z["knife"])[: OH * OW].reshape(OH, OW).astype(bool)
+    ref_mask = np.unpackbits(z["depth_mask"])[: OH * OW].reshape(OH, OW).astype(bool)
+    depth, mask, pts = R.unproject_ref(depth, mask, kinv, count)
+    assert np.array_equal(mask[~knife], ref_mask[~knife]), int((mask != ref_mask)[~knife].sum())
+    sel = ~knife[::6]
+    ref = z["depth_rows"]
+    assert np.all(np.abs(depth[::6][sel] - ref[sel]) <= 1e-6 * np.maximum(np.abs(ref[sel]), 1e-30))
+    sel = ~knife[::6, ::6]
+    rp = z["points_sub"]
+    assert np.all(np.abs(pts[::6, ::6][sel] - rp[sel]) <= 1e-6 * np.maximum(np.abs(rp[sel]), 1e-30))
+    assert (str(z["label_type"]) == "invalid") == (count == 0)

@@ -58,3 +58,72 @@ def test_metrics_reject_cpu_tensors():
         M.rel_depth(torch.ones(4), torch.ones(4))
     with pytest.raises(RuntimeError, match="GPU tensors only"):
         M.masked_nearest_resize(mask=torch.ones(8, 8, dtype=torch.bool), size=(4, 4), return_index=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the numpy references of tests/eval_reference.py (what the GPU sweeps compare the kernels with) against the reference's stored results
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def variant_sources(pred):
+    """the tensor each stored variant of a fixture transforms (metrics.py:134-280 fall-back chains)"""
+    src = {"depth_metric": pred.get("depth_metric"), "depth_scale_invariant": pred.get("depth_scale_invariant", pred.get("depth_metric")),
+           "depth_affine_invariant": next((pred[k] for k in ("depth_affine_invariant", "depth_scale_invariant", "depth_metric") if k in pred), None),
+           "points_metric": pred.get("points_metric"), "points_scale_invariant": pred.get("points_scale_invariant", pred.get("points_metric")),
+           "points_affine_invariant": next((pred[k] for k in ("points_affine_invariant", "points_scale_invariant", "points_metric") if k in pred), None)}
+    if "disparity_affine_invariant" in pred:
+        src["disparity_affine_invariant"] = pred["disparity_affine_invariant"]
+    else:
+        src["disparity_affine_invariant"] = 1 / next(pred[k] for k in ("depth_scale_invariant", "depth_metric") if k in pred)
+    return src
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_error_pass_reference_matches_fixture(name):
+    from tests.eval_reference import error_pass_ref
+    z = load(name)
+    pred, gt = inputs(z, device="cpu")
+    ref = json.loads(str(z["metrics"]))
+    mask = gt["depth_mask"].numpy()
+    n = int(mask.sum())
+    src = variant_sources(pred)
+    for k, prm in zip(json.loads(str(z["variant_names"])), z["variant_params"]):
+        dim = 3 if k.startswith("points") else 1
+        g = gt["points"] if dim == 3 else gt["depth"]
+        s, d1, cnt = error_pass_ref(src[k].numpy(), g.numpy(), mask, prm[None], dim)[0]
+        assert cnt == n
+        assert abs(s / n - ref[k]["rel"]) <= 1e-5 * abs(ref[k]["rel"]), (k, s / n, ref[k]["rel"])
+        assert int(d1) == round(ref[k]["delta1"] * n), (k, d1, ref[k]["delta1"] * n)
+
+
+@pytest.mark.parametrize("name", ["b_ibims", "c_depth_only", "d_moge1"])
+def test_boundary_reference_matches_fixture(name):
+    from tests.eval_reference import boundary_counts_ref, boundary_f1_ref
+    z = load(name)
+    pred, gt = inputs(z, device="cpu")
+    pda = pred_depth_aligned(z, pred).numpy()
+    for r in (1, 2, 3):
+        f1 = boundary_f1_ref(boundary_counts_ref(pda, gt["depth"].numpy(), gt["depth_mask"].numpy(), r))
+        assert abs(f1 - z["boundary_f1"][r - 1]) <= 1e-6, (r, f1, z["boundary_f1"][r - 1])
+
+
+def test_segment_reference_matches_fixture():
+    """per stored segment (id, lr count, diameter, scale, shift xyz, rel, delta1; the reference fills the last six for kept segments only):
+    the low-resolution count, and for kept segments the diameter and the per-segment error at the reference's own scale and shift"""
+    from tests.eval_reference import segment_error_ref, segments_ref
+    z = load("b_ibims")
+    pred, gt = inputs(z, device="cpu")
+    labels = sorted(set(gt["segmentation_labels"].values()))
+    seg, mask, gtp = gt["segmentation_mask"].numpy(), gt["depth_mask"].numpy(), gt["points"].numpy()
+    got = dict(zip(labels, segments_ref(seg, mask, gtp, labels, z["lr_mask"], z["lr_index"])))
+    pp = pred["points_scale_invariant"].numpy()
+    kept = 0
+    for row in z["segments"]:
+        s = got[int(row[0])]
+        assert s["lr_count"] == int(row[1]), row
+        if row[1] < 10:
+            continue
+        kept += 1
+        assert float(s["diameter"]) == row[2], (row, s["diameter"])
+        rel, d1, n = segment_error_ref(seg, mask, pp, gtp, int(row[0]), row[3], row[4:7], s["diameter"])
+        assert abs(rel / n - row[7]) <= 1e-5 * abs(row[7]), (row, rel / n)
+        assert d1 == round(row[8] * n), (row, d1, row[8] * n)
+    assert kept >= 10
