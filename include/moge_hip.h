@@ -349,6 +349,17 @@ int moge_align_l1(const float* x, const float* y, const float* w, int rows, int 
  * from the components selected by comp_mask (bit c = component c); outputs as moge_align_l1 over the n*d residuals (n*d <= 15360). */
 int moge_align_l1_anchored(const float* src, const float* tgt, const float* weight, int n, int d, int comp_mask, const int32_t* row_batch,
                            const int32_t* row_anchor, int rows, float eps, float* scale, float* loss, int32_t* index, void* stream);
+/* alignment.py:91-144, the truncated objective of the training losses: per row a[r] = argmin_a sum_i min(trunc, w[r,i] |a x[r,i] - y[r,i]|) over
+ * the extrema the reference considers, loss[r] = that sum, index[r] = the element whose ratio y/x the solution is (ties: the last element).
+ * trunc is one scalar for all rows.  1 <= n <= 15360, otherwise MOGE_ERR_INVALID.  Long rows stage in device workspace: pass at least
+ * moge_align_trunc_workspace(n, rows) bytes (0 for rows that fit a CU's LDS; then workspace may be NULL).  The anchored form solves the rows of
+ * moge_align_l1_anchored (n*d residuals each); moge_align_select picks the best anchor as for the untruncated solve. */
+int moge_align_trunc_workspace(int n, int rows, int64_t* bytes);
+int moge_align_trunc(const float* x, const float* y, const float* w, int rows, int n, float trunc, float eps, void* workspace, float* a, float* loss,
+                     int32_t* index, void* stream);
+int moge_align_trunc_anchored(const float* src, const float* tgt, const float* weight, int n, int d, int comp_mask, const int32_t* row_batch,
+                              const int32_t* row_anchor, int rows, float trunc, float eps, void* workspace, float* scale, float* loss, int32_t* index,
+                              void* stream);
 /* scatter_min of alignment.py:13-20 along dim 0: per batch element the minimum loss over its rows and the (last) row attaining it; -1 if none */
 int moge_align_select(const float* loss, const int32_t* row_batch, int rows, int batch, float* min_loss, int32_t* min_row, void* stream);
 /* alignment.py:399-415: per row the least-squares (a, b) of sqrt(w) x a + b ~ sqrt(w) y; w may be NULL (all ones); x, y, w are (rows, n) */

@@ -137,6 +137,9 @@ def _load(path: str = LIB_PATH, mode: int = C.RTLD_GLOBAL) -> C.CDLL:
         "moge_test_recover": (C.c_int, [f32p, vp, f32p, i32, i32, i32, f32p, f32p, vp, vp]),
         "moge_align_l1": (C.c_int, [f32p, f32p, f32p, i32, i32, C.c_float, f32p, f32p, vp, vp]),
         "moge_align_l1_anchored": (C.c_int, [f32p, f32p, f32p, i32, i32, i32, vp, vp, i32, C.c_float, f32p, f32p, vp, vp]),
+        "moge_align_trunc_workspace": (C.c_int, [i32, i32, C.POINTER(i64)]),
+        "moge_align_trunc": (C.c_int, [f32p, f32p, f32p, i32, i32, C.c_float, C.c_float, vp, f32p, f32p, vp, vp]),
+        "moge_align_trunc_anchored": (C.c_int, [f32p, f32p, f32p, i32, i32, i32, vp, vp, i32, C.c_float, C.c_float, vp, f32p, f32p, vp, vp]),
         "moge_align_select": (C.c_int, [f32p, vp, i32, i32, f32p, vp, vp]),
         "moge_align_lstsq": (C.c_int, [f32p, f32p, f32p, i32, i32, f32p, f32p, vp]),
         "moge_metrics_lr_sample": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -179,7 +182,8 @@ EXPORTS = ["moge_abi_version", "moge_last_error", "moge_create", "moge_create_v1
            "moge_postprocess", "moge_depth_edge_mask", "moge_cast_f16", "moge_sync", "moge_profile_enable", "moge_profile_read", "moge_debug_tap", "moge_tune_set", "moge_test_gemm",
            "moge_test_gemm_ex", "moge_test_layernorm", "moge_test_attention", "moge_test_conv3x3", "moge_test_conv_ex", "moge_test_convt2x2", "moge_test_ct3", "moge_test_preprocess",
            "moge_test_resize_bicubic_aa", "moge_test_groupnorm_relu", "moge_test_norm_act", "moge_test_posembed", "moge_test_recover",
-           "moge_align_l1", "moge_align_l1_anchored", "moge_align_select", "moge_align_lstsq",
+           "moge_align_l1", "moge_align_l1_anchored", "moge_align_trunc_workspace", "moge_align_trunc", "moge_align_trunc_anchored",
+           "moge_align_select", "moge_align_lstsq",
            "moge_metrics_lr_sample", "moge_metrics_error", "moge_metrics_masked_max", "moge_metrics_boundary", "moge_metrics_segment_stats",
            "moge_metrics_segment_pack", "moge_metrics_segment_error",
            "moge_eval_lanczos_workspace", "moge_eval_lanczos", "moge_eval_masked_nearest", "moge_eval_resize_nearest", "moge_eval_remap",
