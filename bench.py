@@ -1,6 +1,6 @@
 """bench.py - throughput of the MI355X-native `MoGeModel.infer()` hot path (driver contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is ONE infer() pass of the hot path over one batch of synthetic images that are already resident in HBM.
 Workload (BASELINE.json metric: images/sec, moge-2-vitl 518x518 fp16): configs[2] = moge-2-vitl (no normal head),
@@ -15,7 +15,12 @@ not already running under torch.distributed.run (WORLD_SIZE unset) it re-execute
 The workload is the SAME at every N (moge-2-vitl, the config BASELINE.json's metric names, 32 images per GPU) so that the per-N values
 form one weak-scaling curve; `--config moge-2-vitl-normal` is BASELINE configs[3], `--shape mixed` configs[4].
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set-up, W warm-up steps, K timed steps, the
+--dump-outputs files if asked for, and the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload
+description; for N>1 `value` and `ms_per_step` use the slowest rank's timed region).  `--full` runs everything else after the timed region,
+which is the same in both forms: a check that the last timed step's intrinsics are finite and the untimed passes behind the extra objects below.
+Extra objects (`--full` only):
+  p50_latency_ms_batch1  median of one-image infer() calls
   roofline        the dominant kernel, gemm_pp128p_kernel (every launch of it and nothing else: profiler class gemm_pp): algorithmic FLOPs /
                   HIP-event time on the launch stream over the same K steps run single-stream right after the timed region; `traffic` =
                   fabric bytes per launch from the committed rocprofv3 PMC passes (moge_amd/pmc_traffic.json, default workload only; flagged
@@ -276,13 +281,16 @@ def main():
     ap.add_argument("--num-tokens", type=int, default=None)
     ap.add_argument("--shape", default=f"{IMG}x{IMG}", help="HxW of the synthetic images; 'mixed' = half 518x1036, half 1036x518 "
                                                            "(BASELINE configs[4]: two same-shape sub-batches per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive pipeline leg and the blob load-time comparison")
-    ap.add_argument("--no-profile", action="store_true", help="disable the per-kernel HIP-event profiler")
-    ap.add_argument("--no-power", action="store_true", help="skip the untimed power-sampling pass (socket watts / joules per image)")
-    ap.add_argument("--no-autocast-pass", action="store_true", help="skip the extra steps in the reference's other fp16 form (fp32 weights + use_fp16); "
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every untimed extra (power, per-kernel profile and roofline, "
+                                                         "batch-1 latency, the other fp16 form, PCIe pipeline, load times, CPU baseline; "
+                                                         "the --no-* switches below drop single ones) and report them in the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the PCIe-inclusive pipeline leg and the blob load-time comparison")
+    ap.add_argument("--no-profile", action="store_true", help="--full: disable the per-kernel HIP-event profiler")
+    ap.add_argument("--no-power", action="store_true", help="--full: skip the untimed power-sampling pass (socket watts / joules per image)")
+    ap.add_argument("--no-autocast-pass", action="store_true", help="--full: skip the extra steps in the reference's other fp16 form (fp32 weights + use_fp16); "
                                                                      "rocprofv3 passes use it so that the trace holds the headline mode's kernels only")
-    ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency leg (rocprofv3 passes that want the batch-32 launches only)")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the batch-1 latency leg (rocprofv3 passes that want the batch-32 launches only)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="run only the cpu_baseline leg (no GPU needed) and print it")
     ap.add_argument("--print-launch", action="store_true", help="print the torch.distributed.run command --gpus N would re-execute as, and exit")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="process-group backend for N > 1 (nccl = RCCL over xGMI: production; gloo: "
@@ -357,12 +365,13 @@ def main():
         broadcast_weights(model, src=0)                  # one-time RCCL broadcast of the master blob
         dist.barrier()
         tb = time.perf_counter() - tb
-        ones = torch.ones(1, device=dev if args.backend == "nccl" else "cpu")
-        dist.all_reduce(ones)                            # how many ranks RCCL actually joined
-        rccl = {"rccl_ranks": int(ones.item()), "backend": dist.get_backend(), "weight_broadcast_bytes": int(model.master_blob().numel()),
-                "weight_broadcast_seconds": round(tb, 4)}
-        if args.single_device:
-            rccl["single_device"] = True
+        if args.full:
+            ones = torch.ones(1, device=dev if args.backend == "nccl" else "cpu")
+            dist.all_reduce(ones)                            # how many ranks RCCL actually joined
+            rccl = {"rccl_ranks": int(ones.item()), "backend": dist.get_backend(), "weight_broadcast_bytes": int(model.master_blob().numel()),
+                    "weight_broadcast_seconds": round(tb, 4)}
+            if args.single_device:
+                rccl["single_device"] = True
     torch.cuda.synchronize(dev)
     tp = time.perf_counter()
     model.half()                                         # per-rank repack of the fp32 master into the fp16 kernel layouts, on the device
@@ -404,7 +413,7 @@ def main():
     elapsed = time.perf_counter() - t0
     # power pass (rank 0, untimed): the same K steps once more with the sampler thread running
     power = None
-    if rank == 0 and not args.no_power:
+    if args.full and rank == 0 and not args.no_power:
         try:
             with PowerSampler(dev_index) as ps:
                 tpw = time.perf_counter()
@@ -415,14 +424,14 @@ def main():
             power = ps.summary(max(args.steps, 8) * B, tpw)
         except Exception as e:                              # noqa: BLE001  (a measurement extra must not fail the bench)
             power = {"error": str(e)[:200]}
-    if world > 1:
+    if args.full and world > 1:
         dist.barrier()
     # per-kernel-class HIP-event profile: the SAME K steps again with events around every launch (on the launch stream).
     # The profiler serialises the two half-batch streams of the production path (a kernel's event bracket must see only that
     # kernel), so it runs right after the timed region instead of inside it; its own step time is reported alongside.
     prof = None
     prof_ms_per_step = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         model.profile(True)
         model.profile_read(reset=True)
         step()
@@ -440,30 +449,32 @@ def main():
         t = torch.tensor([elapsed, startup_s], device=cdev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, startup_max = float(t[0].item()), float(t[1].item())
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, round(startup_s, 2))
-        if rccl is not None:
+        if args.full:
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, round(startup_s, 2))
             rccl["startup_seconds_max_over_ranks"] = round(startup_max, 2)
             rccl["startup_seconds_per_rank"] = per_rank
-    assert bool(torch.isfinite(out[-1]["intrinsics"]).all())
+    if args.full:
+        assert bool(torch.isfinite(out[-1]["intrinsics"]).all())
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = world * B * args.steps / elapsed
         # B=1 latency (p50), outside the timed region
         lat = []
-        x1 = x[:1].contiguous()
-        for i in range(3 if args.no_latency else 12):
-            torch.cuda.synchronize(dev)
-            t1 = time.perf_counter()
-            model.infer(x1, **kw)
-            torch.cuda.synchronize(dev)
-            lat.append((time.perf_counter() - t1) * 1e3)
-        lat = sorted(lat[2:])
+        if args.full:
+            x1 = x[:1].contiguous()
+            for i in range(3 if args.no_latency else 12):
+                torch.cuda.synchronize(dev)
+                t1 = time.perf_counter()
+                model.infer(x1, **kw)
+                torch.cuda.synchronize(dev)
+                lat.append((time.perf_counter() - t1) * 1e3)
+            lat = sorted(lat[2:])
         # the reference's OTHER fp16 form, for transparency (never `value`): fp32 weights + use_fp16=True = torch.autocast (v2.py:241), which keeps
         # the residual stream in fp32 (MOGE_FP16) - `value` above is model.half() (scripts/infer.py:83-84), whose stream is fp16 (MOGE_FP16_HALF)
         autocast_rate = None
-        if not args.no_autocast_pass:
+        if args.full and not args.no_autocast_pass:
             model.float()
             for _ in range(2):
                 step()
@@ -481,11 +492,12 @@ def main():
             "config": {"workload": f"{args.config} infer(): batch {B}/GPU x 3x{args.shape} torch.rand, num_tokens {num_tokens}, "
                                    f"fp16 weights, synthetic checkpoint (seed 0), inputs resident in HBM, outputs left on device",
                        "global_batch": world * B, "parallelism": f"dp{world} (independent shards, one-time RCCL weight broadcast)"},
-            "p50_latency_ms_batch1": round(lat[len(lat) // 2], 3),
-            "fp16_forms": {"value_is": "model.half(): fp16 weights and fp16 residual stream, as the reference's `--fp16` (scripts/infer.py:83-84)",
-                           "autocast_fp32_weights_images_per_s": round(autocast_rate, 3) if autocast_rate is not None else None,
-                           "note": "infer(use_fp16=True) on fp32 weights = torch.autocast in the reference (v2.py:241): residual stream stays fp32; this rank only"},
         }
+        if args.full:
+            res["p50_latency_ms_batch1"] = round(lat[len(lat) // 2], 3)
+            res["fp16_forms"] = {"value_is": "model.half(): fp16 weights and fp16 residual stream, as the reference's `--fp16` (scripts/infer.py:83-84)",
+                                 "autocast_fp32_weights_images_per_s": round(autocast_rate, 3) if autocast_rate is not None else None,
+                                 "note": "infer(use_fp16=True) on fp32 weights = torch.autocast in the reference (v2.py:241): residual stream stays fp32; this rank only"}
         if rccl is not None:
             res["rccl"] = rccl
         if power is not None:
@@ -570,7 +582,7 @@ def main():
                                  "note": "kernel classes / roofline: HIP events on the launch stream over K single-stream steps run "
                                          "right after the timed region (same inputs); the timed region runs the production path "
                                          "(two half-batch streams, no events)"}
-        if world == 1 and not args.no_pcie and args.shape != "mixed":
+        if args.full and world == 1 and not args.no_pcie and args.shape != "mixed":
             # PCIe-inclusive rate of the caller-side pipeline (never `value`): uint8 host batches in, all maps back to pinned host memory,
             # transfers of neighbouring batches overlapped with the kernels (moge_amd/pipeline.py); also the load-time comparison of the
             # packed master blob against the .pt checkpoint
@@ -616,7 +628,7 @@ def main():
             res["load_seconds"] = {"checkpoint_pt": round(t_pt, 3), "master_blob": round(t_bl, 3), "pack_fp16_on_device": round(pack_s, 4),
                                    "note": "from_pretrained(.pt) vs from_blob(packed fp32 master blob) to a ready fp32 model on the device, page cache warm; pack_fp16_on_device = "
                                            "model.half() of the resident fp32 master (what every rank does after the one-time broadcast)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(O, cfg, sd, x[:1].float().cpu(), kw, args.config, num_tokens)
         if args.dump_outputs:
             dump_outputs(out, args.dump_outputs)

@@ -133,7 +133,7 @@ def test_four_worker_processes_start_and_feed_one_gpu(tmp_path):
     import time
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ["--config", "tiny-vits-normal", "--batch", "4", "--shape", "84x112", "--num-tokens", "108", "--steps", "3", "--warmup", "1",
-              "--no-cpu-baseline", "--no-pcie", "--no-profile"]
+              "--full", "--no-cpu-baseline", "--no-pcie", "--no-profile"]      # --full: the line's `rccl` object (ranks seen, start-up per rank)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
 
     def run(n):

@@ -94,6 +94,21 @@ def test_bench_self_launch_command():
     assert cmd[i + 1:] == ["--gpus", "8", "--steps", "4", "--warmup", "1"]
 
 
+def test_bench_full_reaches_every_rank():
+    """`--full` (the untimed extras after the timed region) is handed on to the ranks of `python bench.py --gpus N --full`."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--no-power", "--print-launch"],
+                         capture_output=True, text=True, env=env, timeout=300)
+    assert out.returncode == 0, out.stderr
+    cmd = json.loads(out.stdout.strip().splitlines()[-1])
+    i = cmd.index(os.path.join(root, "bench.py"))
+    assert cmd[i + 1:] == ["--gpus", "2", "--full", "--no-power"]
+
+
 def _launch_worker_script():
     return (
         "import os, torch, torch.distributed as dist\n"

@@ -5,7 +5,7 @@ key=$1; a=$2; b=$3; rounds=${4:-3}
 out=gpurun_out/ab_$key.log; mkdir -p gpurun_out; : > $out
 for r in $(seq $rounds); do
   for v in $a $b; do
-    env MOGE_$key=$v python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-pcie 2>/dev/null | python3 -c "
+    env MOGE_$key=$v python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-pcie 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 kc = d.get('kernel_classes', {})

@@ -29,12 +29,12 @@ for what in "$@"; do
     kb_conv)    timeout 300 ./tools/kbench conv - 10 > $out/${tag}_kbench_conv.log 2>&1; cat $out/${tag}_kbench_conv.log ;;
     kb_gemm)    KB_PP=1 KB_ROUNDS=3 timeout 400 ./tools/kbench gemm - 10 > $out/${tag}_kbench_gemm.log 2>&1; grep -v "^ " $out/${tag}_kbench_gemm.log | head -80 ;;
     kb_attn)    timeout 300 ./tools/kbench attn - 10 > $out/${tag}_kbench_attn.log 2>&1; cat $out/${tag}_kbench_attn.log ;;
-    bench)      timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-pcie > $out/${tag}_bench.json 2> $out/${tag}_bench.err; cat $out/${tag}_bench.json ;;
-    bench_full) timeout 900 python bench.py > $out/${tag}_bench_full.json 2> $out/${tag}_bench_full.err; cat $out/${tag}_bench_full.json ;;
+    bench)      timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-pcie > $out/${tag}_bench.json 2> $out/${tag}_bench.err; cat $out/${tag}_bench.json ;;
+    bench_full) timeout 900 python bench.py --full > $out/${tag}_bench_full.json 2> $out/${tag}_bench_full.err; cat $out/${tag}_bench_full.json ;;
     ab_conv)    # same box, alternating: new conv forms off / on
                 for r in 1 2; do
                   for v in 0 1; do
-                    MOGE_CONV_RB=$v MOGE_CONV_SIDE_REG=$v timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-pcie 2>/dev/null | python -c "
+                    MOGE_CONV_RB=$v MOGE_CONV_SIDE_REG=$v timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-pcie 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); k = d['kernel_classes']
 print('conv forms $v: %.1f img/s  %.2f ms/step  conv %.2f ms  gemm_pp %.2f  attn %.2f  post %.2f' % (d['value'], d['ms_per_step'], k['conv']['ms_per_step'], k['gemm_pp']['ms_per_step'], k['attn']['ms_per_step'], k['post']['ms_per_step']))"
@@ -51,7 +51,7 @@ print('conv forms $v: %.1f img/s  %.2f ms/step  conv %.2f ms  gemm_pp %.2f  attn
     ab)         # same box, alternating: MOGE_$AB_VAR = 0 / 1 (e.g. AB_VAR=L4DOT)
                 for r in 1 2; do
                   for v in ${AB_VALS:-0 1}; do
-                    env MOGE_${AB_VAR}=$v timeout 300 python bench.py ${BENCH_ARGS} --steps 10 --warmup 3 --no-cpu-baseline --no-pcie 2>/dev/null | python -c "
+                    env MOGE_${AB_VAR}=$v timeout 300 python bench.py ${BENCH_ARGS} --full --steps 10 --warmup 3 --no-cpu-baseline --no-pcie 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); k = d['kernel_classes']
 print('$AB_VAR=$v: %.1f img/s  %.2f ms/step  p50(B=1) %.2f  conv %.2f ms  gemm_pp %.2f  attn %.2f  post %.2f  norm %.2f' % (d['value'], d['ms_per_step'], d['p50_latency_ms_batch1'], k['conv']['ms_per_step'], k['gemm_pp']['ms_per_step'], k['attn']['ms_per_step'], k['post']['ms_per_step'], k['norm']['ms_per_step']))"
@@ -59,7 +59,7 @@ print('$AB_VAR=$v: %.1f img/s  %.2f ms/step  p50(B=1) %.2f  conv %.2f ms  gemm_p
                 done > $out/${tag}_ab_${AB_VAR}${AB_SUFFIX}.log 2>&1; cat $out/${tag}_ab_${AB_VAR}${AB_SUFFIX}.log ;;
     tests_conv) timeout 600 python -m pytest tests/test_hip_conv_ex.py tests/test_hip_parity.py -m gpu -q -p no:cacheprovider > $out/${tag}_pytest_conv.log 2>&1; tail -15 $out/${tag}_pytest_conv.log ;;
     other_cfgs) for a in "--config moge-2-vitb-normal --batch 8" "--config moge-2-vitl-normal" "--shape mixed --config moge-2-vitl-normal" "--num-tokens 1369" "--config moge-2-vits-normal --batch 8"; do
-                  timeout 400 python bench.py $a --steps 10 --warmup 3 --no-cpu-baseline --no-pcie 2>/dev/null | tail -1
+                  timeout 400 python bench.py $a --full --steps 10 --warmup 3 --no-cpu-baseline --no-pcie 2>/dev/null | tail -1
                 done > $out/${tag}_bench_other_configs.jsonl; python -c "
 import json
 for l in open('$out/${tag}_bench_other_configs.jsonl'):
@@ -68,7 +68,7 @@ for l in open('$out/${tag}_bench_other_configs.jsonl'):
     kb_gemm_mrg) for f in qkv proj fc1 fc2 outproj tailM; do KB_PP=1 KB_ROUNDS=3 timeout 300 ./tools/kbench gemm $f 10; done > $out/${tag}_kbench_gemm_mrg.log 2>&1; grep -v "^   ts" $out/${tag}_kbench_gemm_mrg.log | grep -v "b1\.\|b4\.\|vits" ;;
     tests_gemm) MOGE_PP_KERN=${PPK:-3} timeout 600 python -m pytest tests/test_hip_gemm_pp.py -m gpu -q -p no:cacheprovider 2>&1 | tail -5 ;;
     batch_sweep) for r in 1 2; do for b in ${BATCHES:-32 36 18 27}; do
-                  timeout 400 python bench.py --batch $b --steps 8 --warmup 3 --no-cpu-baseline --no-pcie 2>/dev/null | python -c "
+                  timeout 400 python bench.py --batch $b --full --steps 8 --warmup 3 --no-cpu-baseline --no-pcie 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); k = d['kernel_classes']
 print('batch $b: %.1f img/s  %.2f ms/step  (kernel sum single-stream %.2f ms: gemm_pp %.2f attn %.2f conv %.2f)' % (d['value'], d['ms_per_step'], d['whole_path']['kernel_ms_per_step'], k['gemm_pp']['ms_per_step'], k['attn']['ms_per_step'], k['conv']['ms_per_step']))"
@@ -77,13 +77,13 @@ print('batch $b: %.1f img/s  %.2f ms/step  (kernel sum single-stream %.2f ms: ge
     ab_q4)      for cfg in "vitb8:--config moge-2-vitb-normal --batch 8" "vitl8:--batch 8" "vitl4:--batch 4" "vitl16:--batch 16"; do
                   echo "== ${cfg%%:*}"; AB_SUFFIX=_${cfg%%:*} BENCH_ARGS="${cfg#*:}" AB_VAR=ATTN_Q2_MAX_WGS AB_VALS="768 2900" bash tools/gpu_call.sh $tag ab; done ;;
     lat)        # batch-1 anatomy: kernel classes from the HIP-event profiler + a rocprofv3 kernel trace of the same command
-                timeout 300 python bench.py --batch 1 --steps 30 --warmup 5 --no-cpu-baseline --no-pcie > $out/${tag}_bench_b1.json 2>/dev/null
+                timeout 300 python bench.py --batch 1 --full --steps 30 --warmup 5 --no-cpu-baseline --no-pcie > $out/${tag}_bench_b1.json 2>/dev/null
                 python -c "
 import json
 d = json.loads(open('$out/${tag}_bench_b1.json').read().strip().splitlines()[-1]); k = d['kernel_classes']
 print('B=1: %.1f img/s %.3f ms/step p50 %.3f | ' % (d['value'], d['ms_per_step'], d['p50_latency_ms_batch1']) + ' '.join('%s %.3f' % (n, v['ms_per_step']) for n, v in k.items()))"
-                rm -rf /tmp/lt; rocprofv3 --kernel-trace --output-format csv -d /tmp/lt -o lt -- python bench.py --batch 1 --steps 30 --warmup 5 --no-cpu-baseline --no-pcie --no-profile > /dev/null 2>&1
-                python3 tools/trace_summary.py /tmp/lt/lt_kernel_trace.csv 80 > $out/${tag}_b1_kernels_by_grid.csv; head -60 $out/${tag}_b1_kernels_by_grid.csv ;;
+                rm -rf $TMPDIR/lt; rocprofv3 --kernel-trace --output-format csv -d $TMPDIR/lt -o lt -- python bench.py --batch 1 --full --steps 30 --warmup 5 --no-cpu-baseline --no-pcie --no-profile > /dev/null 2>&1
+                python3 tools/trace_summary.py $TMPDIR/lt/lt_kernel_trace.csv 80 > $out/${tag}_b1_kernels_by_grid.csv; head -60 $out/${tag}_b1_kernels_by_grid.csv ;;
     kb_lat)     for f in b1. b4.; do KB_LAT=1 KB_ROUNDS=3 timeout 300 ./tools/kbench gemm $f 20; done > $out/${tag}_kbench_gemm_latency.log 2>&1; grep -v "^   ts" $out/${tag}_kbench_gemm_latency.log ;;
     ab_heads)   for cfg in "vitl1:--batch 1" "vitl4:--batch 4" "vitb8:--config moge-2-vitb-normal --batch 8" "vitln1:--config moge-2-vitl-normal --batch 1" "vitln4:--config moge-2-vitl-normal --batch 4"; do
                   echo "== ${cfg%%:*}"; AB_SUFFIX=_${cfg%%:*} BENCH_ARGS="${cfg#*:}" AB_VAR=HEAD_STREAMS AB_VALS="0 1" bash tools/gpu_call.sh $tag ab; done
