@@ -700,7 +700,7 @@ __global__ __launch_bounds__(256, QB > 2 ? 2 : 3) void attn_pp16mq_kernel(const 
         qblk = s - hs * (int)gridDim.x;
     }
     const int q_base = q_start + qblk * (64 * QB);     // (q_start > 0: the queries attn_pp16x_kernel left over, see launch_attn_pp16)
-    if constexpr (QB == 4) if (xcd_remap & 2) {                 // (bit 1: ATTN_TAIL2, default on)
+    if constexpr (QB == 4) if (xcd_remap & 2) {                 // (bit 1: always set by launch_attn_pp16)
         // The last workgroup of a head with at most 128 queries left (N = 3601: 17 of 256) runs the 32-queries-per-wave body: its one or two
         // waves that hold real queries then compute 2 query blocks each instead of 4 (two of them clamped copies) - the same arithmetic per
         // query (the two instantiations are bit-identical), half the work on the workgroup that decides when its slot is free again.
@@ -829,7 +829,7 @@ static int launch_attn_pp16(const void* q, const void* k, const void* v, void* o
         // 64-query form wins (928 workgroups = 1.2 rounds against 480 = 0.94: 745-797 vs 845-879 TF/s; r03zd_kbench_attn_b1.log)
         const long wgs2 = (long)((Ntok + 127) / 128) * B * nh;
         const bool q4 = akern == 2 || akern == 4 || (akern == 3 && wgs2 > moge_tune_get("ATTN_Q2_MAX_WGS", 3 * pp_device_cus()));
-        const int xr = (moge_tune_get("ATTN_XCD", 1) ? 1 : 0) | (moge_tune_get("ATTN_TAIL2", 1) ? 2 : 0);
+        constexpr int xr = 3;           // the kernels' xcd_remap argument: bit 0 = a head's query blocks on one XCD, bit 1 = the short tail of attn_pp16mq<4> (both always on)
 #ifdef MOGE_EXPERIMENTS
         // attn_pp16x_kernel (ping-pong wave groups, 512 queries per workgroup, ONE workgroup per CU): bit-identical to the two above; taken while
         // its grid still fills the chip at least ATTN_X_MIN_ROUNDS (default 2) times.  ATTN_KERN 4 forces it, ATTN_X = 0 switches it off.

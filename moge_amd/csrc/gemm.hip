@@ -709,12 +709,7 @@ extern "C" void moge_tune_set(const char* key, int value) {
 
 template <typename T, int AMODE>
 static int launch_by_n(const GemmArgs& g, hipStream_t st) {
-    const int g_conv_bm256 = moge_tune_get("CONV_BM256", 0);
     if (g.N > 64) return launch_cfg<T, 2, 2, 2, 2, AMODE>(g, st);     // 128 x 128
-    if (g_conv_bm256 && g.M >= 4096) {
-        if (g.N > 32) return launch_cfg<T, 4, 1, 2, 2, AMODE>(g, st); // 256 x 64
-        return launch_cfg<T, 4, 1, 2, 1, AMODE>(g, st);               // 256 x 32
-    }
     if (g.N > 32) return launch_cfg<T, 4, 1, 1, 2, AMODE>(g, st);     // 128 x 64
     return launch_cfg<T, 4, 1, 1, 1, AMODE>(g, st);                   // 128 x 32
 }
@@ -729,19 +724,23 @@ bool gemm_runs_pp(const GemmArgs& g) {
     return tiles >= moge_tune_get("PP_MIN_TILES", 96);
 }
 
+// The shapes of AMODE_LINEAR that gemm_glds_kernel takes (when the ping-pong kernel does not: gemm_runs_pp)
+template <typename T>
+static bool gemm_glds_eligible(const GemmArgs& g) {
+    return g.N > 64 && !g.relu_in && (g.K % (8 * TT<T>::CH)) == 0;
+}
+
 // LN-fold producers (EPI_RESID + ln_part) that go to gemm_glds_kernel can finalise the statistics themselves (GemmArgs::ln_mr_out): true when launch_gemm<f16>
 // would take that kernel for g - the caller then sets ln_mr_out / ln_cnt and skips launch_ln_finalize.
 bool gemm_fuses_ln_finalize(const GemmArgs& g) {
-    if (!moge_tune_get("LN_FINALIZE_FUSED", 1)) return false;
     if (g.epi != EPI_RESID || !g.ln_part || !g.x16 || (g.N & 63) != 0) return false;
     if (gemm_runs_pp(g)) return false;
-    return g.N > 64 && !g.relu_in && (g.K % (8 * TT<f16>::CH)) == 0 && !moge_tune_get("DISABLE_GLDS", 0);
+    return gemm_glds_eligible<f16>(g);
 }
 
 template <typename T>
 int launch_gemm(const GemmArgs& g, int amode, hipStream_t st) {
     if (g.M <= 0 || g.N <= 0 || g.K <= 0) return -1;
-    const int g_disable_glds = moge_tune_get("DISABLE_GLDS", 0);
     if ((g.K % TT<T>::CH) != 0 || (g.N % 4) != 0) return -1;
     if (amode != AMODE_LINEAR && (g.C % TT<T>::CH) != 0) return -1;
     switch (amode) {
@@ -749,7 +748,7 @@ int launch_gemm(const GemmArgs& g, int amode, hipStream_t st) {
         if constexpr (std::is_same<T, f16>::value) {
             if (gemm_runs_pp(g)) return launch_gemm_pp(g, st);
         }
-        if (g.N > 64 && !g.relu_in && (g.K % (8 * TT<T>::CH)) == 0 && !g_disable_glds) {
+        if (gemm_glds_eligible<T>(g)) {
             // latency regime: when 128x128 tiles do not even give every CU two workgroups, halve the tile rows (64x128; a 3-slab
             // ring = 72 KiB LDS, two co-resident workgroups per CU: at batch 1-2 the weights arrive cold from HBM and the second slab in flight is worth
             // more than a third workgroup - 7.3 -> 6.85 ms per image against the double buffer).  Same MFMA and K order: results are bit-identical.

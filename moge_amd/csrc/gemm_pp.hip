@@ -1381,13 +1381,14 @@ static int launch_pp_any(const GemmArgs& g, hipStream_t st) {
 int launch_gemm_pp(const GemmArgs& g0, hipStream_t st) {
     GemmArgs g = g0;
     g.dbg = moge_tune_get("PP_DBG", 0);
-    g.abl = moge_tune_get("PP_ABL", 0);
+#ifdef MOGE_EXPERIMENTS
+    g.abl = moge_tune_get("PP_ABL", 0);         // (the product build's kernels do not read it)
+#else
+    g.abl = 0;
+#endif
     g.stagger = moge_tune_get("PP_STAGGER", 0);
-    g.stagger_clk = moge_tune_get("PP_STAGGER_CLK", 56000);
-    {
-        const int nt = moge_tune_get("NT_STORE", 0);        // bit 0: GELU (MLP hidden), bit 1: QKV, bit 2: plain stores
-        g.nt_store = (g.epi == EPI_QKV) ? (nt >> 1) & 1 : (g.act == ACT_GELU ? nt & 1 : (nt >> 2) & 1);
-    }
+    g.stagger_clk = 56000;          // (only read when PP_STAGGER > 1)
+    g.nt_store = 0;                 // plain stores: non-temporal ones for the streaming activations measured +-0 (EXPERIMENTS.md)
     switch (epilogue_kind(g)) {
     case EPK_RESID: return launch_pp_any<EPK_RESID>(g, st);
     case EPK_RESID16: return launch_pp_any<EPK_RESID16>(g, st);

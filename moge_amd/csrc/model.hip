@@ -260,7 +260,7 @@ static void build_tables_v2_decoder(moge_handle* h) {
                 if (l == 0) {
                     padd(h, name + ".in0.w", (int64_t)cl * c0);
                     // fp16 path: the summed output projections and this 1x1 block have no non-linearity between them (modules.py:128-131,
-                    // 245): composed at pack time into ONE [c0][n_taps * D] matrix applied to the K-concatenated taps (COMPOSE, below)
+                    // 245): composed at pack time into ONE [c0][n_taps * D] matrix applied to the K-concatenated taps (`compose` in forward_impl)
                     padd(h, name + ".in0c.w", (int64_t)cl * c.n_taps * D);
                     aadd(h, name + ".in0c.bias", cl);
                 }
@@ -473,7 +473,7 @@ static int build_aux(moge_handle* h, hipStream_t st) {
             }
         }
     if (ndot > 0) LCHK(launch_pack_dot_table(A(h, "neck.dot.w2cat"), 4 * ndot, ndot, A(h, "neck.dot"), st));
-    // ---- composed linear chains (fp16 path, COMPOSE): the bias vectors, in double on the host (one-off, a few MB of D2H) ----
+    // ---- composed linear chains (fp16 path, `compose` in forward_impl): the bias vectors, in double on the host (one-off, a few MB of D2H) ----
     {   // neck level 0: in0(sum_k proj_k(tap_k)) = (Win0 Wout) tapcat + (Win0 sum_k b_k + b_in0) + uv term
         std::vector<float> win((size_t)c0 * (c0 + 2)), bo(c0), bi(c0), bc(c0);
         HIPCHK(hipMemcpyAsync(win.data(), M(h, "neck.input_blocks.0.weight"), win.size() * 4, hipMemcpyDeviceToHost, st));
@@ -564,7 +564,7 @@ static int compose_ct3_f16(moge_handle* h, const std::string& name, int l, int c
     return 0;
 }
 
-// Composed linear chains of the fp16 path (COMPOSE): products formed in fp32 from the master weights, ONE rounding to fp16.
+// Composed linear chains of the fp16 path (`compose` / `compose0` in forward_impl): products formed in fp32 from the master weights, ONE rounding to fp16.
 static int compose_weights_f16(moge_handle* h, hipStream_t st) {
     const moge_config& c = h->cfg;
     const int D = c.embed_dim, c0 = c.dims[0], K4 = c.n_taps * D, co = c.dims[1];
@@ -616,11 +616,12 @@ static int pack_weights(moge_handle* h, hipStream_t st) {
     LCHK(launch_repack<T>(M(h, bb + "patch_embed.proj.weight"), Pm<T>(h, "patch.w"), D, 1, 1, KPATCH, KPATCH, 0, 0, 1, KPATCH_PAD, 0, 0, st));
     for (int i = 0; i < c.depth; i++) {
         const std::string p = bb + S("blocks.%d.", i);
-        LCHK((launch_convert<float, T>(M(h, p + "attn.qkv.weight"), Pm<T>(h, S("blk%d.qkv", i)), (long)3 * D * D, st)));
         LCHK((launch_convert<float, T>(M(h, p + "attn.proj.weight"), Pm<T>(h, S("blk%d.proj", i)), (long)D * D, st)));
-        LCHK((launch_convert<float, T>(M(h, p + "mlp.fc1.weight"), Pm<T>(h, S("blk%d.fc1", i)), (long)4 * D * D, st)));
         LCHK((launch_convert<float, T>(M(h, p + "mlp.fc2.weight"), Pm<T>(h, S("blk%d.fc2", i)), (long)4 * D * D, st)));
-        if constexpr (std::is_same<T, f16>::value) {
+        if constexpr (!std::is_same<T, f16>::value) {
+            LCHK((launch_convert<float, T>(M(h, p + "attn.qkv.weight"), Pm<T>(h, S("blk%d.qkv", i)), (long)3 * D * D, st)));
+            LCHK((launch_convert<float, T>(M(h, p + "mlp.fc1.weight"), Pm<T>(h, S("blk%d.fc1", i)), (long)4 * D * D, st)));
+        } else {                    // encode<f16> reads the LN-folded forms only
             LCHK(launch_fold_ln<f16>(M(h, p + "attn.qkv.weight"), M(h, p + "norm1.weight"), M(h, p + "norm1.bias"), M(h, p + "attn.qkv.bias"),
                                      Pm<T>(h, S("blk%d.qkvf", i)), A(h, S("blk%d.qkv.c", i)), A(h, S("blk%d.qkv.bf", i)), 3 * D, D, st));
             LCHK(launch_fold_ln<f16>(M(h, p + "mlp.fc1.weight"), M(h, p + "norm2.weight"), M(h, p + "norm2.bias"), M(h, p + "mlp.fc1.bias"),
@@ -849,7 +850,7 @@ static int conv3x3(moge_handle* h, const T* in, const T* w, const float* bias, T
     g.pixW = Ww; g.pixH = Hh;
     if (uv) g.uv = *uv;
     if (fused) *fused = false;
-    if (side && std::is_same<T, f16>::value && Cin == Cout && moge_tune_get("CONV_PP", 1) && moge_tune_get("FUSE_IN", 1)) {
+    if (side && std::is_same<T, f16>::value && Cin == Cout && moge_tune_get("CONV_PP", 1)) {
         // fused 1x1 side input (x + in_l(neck_l), modules.py:245): only the halo kernel implements it; `bias` must already hold
         // the sum of both biases (the caller passes the combined vector when *fused comes back true, see below)
         GemmArgs g2 = g;
@@ -1026,6 +1027,9 @@ static int encode(moge_handle* h, const void* image, int img_dtype, int imgH, in
     const moge_config& c = h->cfg;
     const int D = c.embed_dim, nh = c.num_heads, L = c.depth, c0 = c.dims[0];
     const int B = pl.B, rows = pl.rows, cols = pl.cols, Np = pl.Np, Ntok = pl.Ntok, Npad = pl.Npad;
+    // fp16 = the throughput path: V row-major + attention_pp (LDS-DMA, transposed LDS reads) and the LN fold (below); fp32 = the parity path:
+    // V^T + attention.hip, LayerNorm kernels
+    constexpr bool fp16 = std::is_same<T, f16>::value;
     char* ws = h->ws + pl.base;
     T* patches = (T*)(ws + pl.patches);
     float* x = (float*)(ws + pl.x);
@@ -1049,8 +1053,7 @@ static int encode(moge_handle* h, const void* image, int img_dtype, int imgH, in
         // counters (a hipMemsetAsync = two fill kernels before), and the patch-embed epilogue writes the cls rows (cls_row_kernel before): four launches
         // fewer in front of the first block, the same bits.  (--experiments builds with the stream-K attention workspace: its counters sit behind the LN
         // counters, one range.)
-        const bool attn_pp0 = std::is_same<T, f16>::value && moge_tune_get("ATTN_PP", 1) != 0;
-        const bool has_attn_ws = attn_pp0 && pl.attn_ws_bytes;
+        const bool has_attn_ws = fp16 && pl.attn_ws_bytes;
         int* zero_p = pl.ln_cnt_bytes ? (int*)(ws + pl.ln_cnt) : (has_attn_ws ? (int*)(ws + pl.attn_ws) : nullptr);
         const size_t zero_bytes = pl.ln_cnt_bytes ? (has_attn_ws ? (pl.attn_ws - pl.ln_cnt) + attention_pp_ws_counter_bytes(B, nh, Ntok) : pl.ln_cnt_bytes)
                                                   : (has_attn_ws ? attention_pp_ws_counter_bytes(B, nh, Ntok) : 0);
@@ -1068,11 +1071,9 @@ static int encode(moge_handle* h, const void* image, int img_dtype, int imgH, in
         g.cls = M(h, bb + "cls_token");
         CHK(run_gemm<T>(h, g, AMODE_LINEAR, MOGE_KC_GEMM, st, KPATCH));
     }
-    // fp16 throughput path: V row-major + attention_pp (LDS-DMA, transposed LDS reads); fp32 parity path: V^T + attention.hip
-    const bool attn_pp = std::is_same<T, f16>::value && moge_tune_get("ATTN_PP", 1) != 0;
-    if (!attn_pp) HIPCHK(hipMemsetAsync(vT, 0, (size_t)B * D * Npad * sizeof(T), st));      // zero the key padding of V^T
+    if (!fp16) HIPCHK(hipMemsetAsync(vT, 0, (size_t)B * D * Npad * sizeof(T), st));      // zero the key padding of V^T
     // stream-K attention (--experiments builds; one image: 464 workgroups on 768 slots): its per-query-block counters start at zero (preprocess_kernel above); the kernel leaves them zero
-    void* attn_ws = attn_pp && pl.attn_ws_bytes ? (void*)(ws + pl.attn_ws) : nullptr;
+    void* attn_ws = fp16 && pl.attn_ws_bytes ? (void*)(ws + pl.attn_ws) : nullptr;
     int* ln_cnt = pl.ln_cnt_bytes ? (int*)(ws + pl.ln_cnt) : nullptr;       // fused LN finalize (latency-regime GEMMs): row-block counters, zeroed by preprocess_kernel
 
     // ---- ViT blocks (block.py:110-112) -----------------------------------------------------------------------------
@@ -1080,17 +1081,17 @@ static int encode(moge_handle* h, const void* image, int img_dtype, int imgH, in
     // fc1 GEMMs read the fp16 COPY of the raw residual (written by the previous RESID epilogue next to its (sum, sum of squares) partials)
     // and apply (mean, rstd) in their epilogues.  Removes 2 x 0.7 GB of LayerNorm traffic per block; the final-norm taps still run
     // layernorm_kernel on the fp32 residual.  The statistics' summation tree is the same in gemm.hip and gemm_pp.hip (batch invariance).
-    const bool ln_fold = std::is_same<T, f16>::value && (D % 64) == 0 && moge_tune_get("LN_FOLD", 1) != 0;
+    // (The folded GEMMs need D % 64 == 0: moge_create / moge_create_v1 only accept multiples of 128.)
     // `.half()` models (MOGE_FP16_HALF): the residual stream lives in `xn` as fp16 from the first block on - the proj / fc2 epilogues update it in
-    // place (EPK_RESID16) and the fp32 stream `x` is only the patch-embedding output.  Needs the LN fold (its operand IS the raw stream).
-    const bool half_resid = ln_fold && h->half_resid && moge_tune_get("HALF_RESID", 1) != 0;
+    // place (EPK_RESID16) and the fp32 stream `x` is only the patch-embedding output.  Rides on the LN fold (its operand IS the raw stream).
+    const bool half_resid = fp16 && h->half_resid;
     float* ln_part = (float*)(ws + pl.ln_part);
     float* ln_mr = (float*)(ws + pl.ln_mr);
     int tap_k = 0;
     bool ln_done = false;          // the producer GEMM in front has written (mean, rstd) itself: no ln_finalize launch
     for (int i = 0; i < L; i++) {
         const std::string p = bb + S("blocks.%d.", i);
-        if (!ln_fold) {
+        if (!fp16) {
             ProfScope ps(h, st, MOGE_KC_NORM, 0, (double)BN * D * (4 + sizeof(T)));
             LCHK(launch_layernorm<T>(x, M(h, p + "norm1.weight"), M(h, p + "norm1.bias"), xn, nullptr, BN, D, D, 0, 0, Ntok, st));
         } else if (i == 0) {
@@ -1102,17 +1103,17 @@ static int encode(moge_handle* h, const void* image, int img_dtype, int imgH, in
         }
         {
             GemmArgs g = gemm_args();
-            g.a = xn; g.lda = D; g.w = P<T>(h, S(ln_fold ? "blk%d.qkvf" : "blk%d.qkv", i)); g.ldw = D;
+            g.a = xn; g.lda = D; g.w = P<T>(h, S(fp16 ? "blk%d.qkvf" : "blk%d.qkv", i)); g.ldw = D;
             g.M = (int)BN; g.N = 3 * D; g.K = D;
             g.epi = EPI_QKV; g.bias = M(h, p + "attn.qkv.bias"); g.q = qb; g.k = kb; g.vT = vT;
-            if (ln_fold) { g.bias = A(h, S("blk%d.qkv.bf", i)); g.ln_mr = ln_mr; g.ln_c = A(h, S("blk%d.qkv.c", i)); }
-            g.nh = nh; g.Npad = Npad; g.D = D; g.Ntok = Ntok; g.v_rowmajor = attn_pp ? 1 : 0;
+            if (fp16) { g.bias = A(h, S("blk%d.qkv.bf", i)); g.ln_mr = ln_mr; g.ln_c = A(h, S("blk%d.qkv.c", i)); }
+            g.nh = nh; g.Npad = Npad; g.D = D; g.Ntok = Ntok; g.v_rowmajor = fp16 ? 1 : 0;
             g.qscale = 0.125f * 1.4426950408889634f;       // 1/sqrt(64) * log2(e): attention works in exp2
             CHK(run_gemm<T>(h, g, AMODE_LINEAR, MOGE_KC_GEMM, st));
         }
         {
             ProfScope ps(h, st, MOGE_KC_ATTN, 4.0 * B * nh * (double)Ntok * Ntok * 64, (double)BN * D * 4 * sizeof(T));
-            if (attn_pp) LCHK(launch_attention_pp(qb, kb, vT, attn, B, nh, Ntok, st, attn_ws, pl.attn_ws_bytes));
+            if (fp16) LCHK(launch_attention_pp(qb, kb, vT, attn, B, nh, Ntok, st, attn_ws, pl.attn_ws_bytes));
             else LCHK(launch_attention<T>(qb, kb, vT, attn, B, nh, Ntok, Npad, st));
         }
         {
@@ -1120,13 +1121,13 @@ static int encode(moge_handle* h, const void* image, int img_dtype, int imgH, in
             g.a = attn; g.lda = D; g.w = P<T>(h, S("blk%d.proj", i)); g.ldw = D;
             g.M = (int)BN; g.N = D; g.K = D;
             g.epi = EPI_RESID; g.bias = M(h, p + "attn.proj.bias"); g.xres = x; g.ldc = D; g.gamma = M(h, p + "ls1.gamma");
-            if (ln_fold) { g.x16 = xn; g.ln_part = ln_part; }
+            if (fp16) { g.x16 = xn; g.ln_part = ln_part; }
             if (half_resid) g.xres = nullptr;
-            ln_done = ln_fold && ln_cnt && gemm_fuses_ln_finalize(g);     // latency regime: the GEMM's last column tile of a row block writes (mean, rstd)
+            ln_done = fp16 && ln_cnt && gemm_fuses_ln_finalize(g);     // latency regime: the GEMM's last column tile of a row block writes (mean, rstd)
             if (ln_done) { g.ln_mr_out = ln_mr; g.ln_cnt = ln_cnt; }
             CHK(run_gemm<T>(h, g, AMODE_LINEAR, MOGE_KC_GEMM, st));
         }
-        if (!ln_fold) {
+        if (!fp16) {
             ProfScope ps(h, st, MOGE_KC_NORM, 0, (double)BN * D * (4 + sizeof(T)));
             LCHK(launch_layernorm<T>(x, M(h, p + "norm2.weight"), M(h, p + "norm2.bias"), xn, nullptr, BN, D, D, 0, 0, Ntok, st));
         } else if (!ln_done) {
@@ -1135,10 +1136,10 @@ static int encode(moge_handle* h, const void* image, int img_dtype, int imgH, in
         }
         {
             GemmArgs g = gemm_args();
-            g.a = xn; g.lda = D; g.w = P<T>(h, S(ln_fold ? "blk%d.fc1f" : "blk%d.fc1", i)); g.ldw = D;
+            g.a = xn; g.lda = D; g.w = P<T>(h, S(fp16 ? "blk%d.fc1f" : "blk%d.fc1", i)); g.ldw = D;
             g.M = (int)BN; g.N = 4 * D; g.K = D;
             g.epi = EPI_STORE; g.act = ACT_GELU; g.bias = M(h, p + "mlp.fc1.bias"); g.out = hidden; g.ldc = 4 * D;
-            if (ln_fold) { g.bias = A(h, S("blk%d.fc1.bf", i)); g.ln_mr = ln_mr; g.ln_c = A(h, S("blk%d.fc1.c", i)); }
+            if (fp16) { g.bias = A(h, S("blk%d.fc1.bf", i)); g.ln_mr = ln_mr; g.ln_c = A(h, S("blk%d.fc1.c", i)); }
             CHK(run_gemm<T>(h, g, AMODE_LINEAR, MOGE_KC_GEMM, st));
         }
         {
@@ -1146,9 +1147,9 @@ static int encode(moge_handle* h, const void* image, int img_dtype, int imgH, in
             g.a = hidden; g.lda = 4 * D; g.w = P<T>(h, S("blk%d.fc2", i)); g.ldw = 4 * D;
             g.M = (int)BN; g.N = D; g.K = 4 * D;
             g.epi = EPI_RESID; g.bias = M(h, p + "mlp.fc2.bias"); g.xres = x; g.ldc = D; g.gamma = M(h, p + "ls2.gamma");
-            if (ln_fold && i + 1 < L) { g.x16 = xn; g.ln_part = ln_part; }
+            if (fp16 && i + 1 < L) { g.x16 = xn; g.ln_part = ln_part; }
             if (half_resid) { g.xres = nullptr; g.x16 = xn; }          // (last block: no statistics wanted, the stream is still updated)
-            ln_done = ln_fold && ln_cnt && gemm_fuses_ln_finalize(g);     // (block i + 1's qkv reads ln_mr)
+            ln_done = fp16 && ln_cnt && gemm_fuses_ln_finalize(g);     // (block i + 1's qkv reads ln_mr)
             if (ln_done) { g.ln_mr_out = ln_mr; g.ln_cnt = ln_cnt; }
             CHK(run_gemm<T>(h, g, AMODE_LINEAR, MOGE_KC_GEMM, st));
         }
@@ -1189,21 +1190,25 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
     float* cls = (float*)(ws + pl.cls);
     T* feat = (T*)(ws + pl.feat);
     const long BN = (long)B * Ntok, BP = (long)B * Np;
-    // fp16 path: chains of linear layers with nothing between them are composed at pack time (compose_weights_f16): the summed output
-    // projections + the neck's level-0 input block become one GEMM on the K-concatenated taps (`feat` is never formed), and a head without
-    // level-0 residual blocks applies (ConvTranspose2d . input block) to the neck's level-0 map in one GEMM.  Same mathematics, fewer
-    // roundings; the fp32 parity path keeps the reference's layer-by-layer order.
-    const bool compose = std::is_same<T, f16>::value && moge_tune_get("COMPOSE", 1) != 0;
+    // ---- the fusions of the fp16 path, decided here once from the config; the fp32 parity path keeps the reference's layer-by-layer order ----
+    constexpr bool fp16 = std::is_same<T, f16>::value;
+    // compose: chains of linear layers with nothing between them are composed at pack time (compose_weights_f16): the summed output
+    // projections + the neck's level-0 input block become one GEMM on the K-concatenated taps (`feat` is never formed).  Same mathematics, fewer roundings.
+    const bool compose = fp16;
+    // compose0: a head without level-0 residual blocks applies (ConvTranspose2d . input block) to the neck's level-0 map in one GEMM
+    const bool compose0 = compose && c.head_res_blocks[0] == 0 && c.head_resamplers[0] == MOGE_RS_CONV_TRANSPOSE;
+    // fuse_in: at levels >= 1 the head's `x + in_l(neck_l)` (modules.py:245) rides in the resampler's last conv as a 1x1 side input, where the halo kernel takes the shape
+    const bool fuse_in = fp16;
+    // fuse_l4: level 4 without residual blocks - the input block is folded into the output conv (head_final_kernel)
+    const bool fuse_l4 = fp16 && c.head_res_blocks[MOGE_LEVELS - 1] == 0;
+    // l4dot: ... and with 64 -> 32 channels on phase resamplers, out_k(x4_k + in4_k(n4)) = Wout_k x4_k + (Wout_k Win4_k) n4 + b2_k is evaluated
+    // INSIDE the two 64 -> 4 x 32 resampler convs (conv_pp.hip, fused output conv); head_final only resizes and remaps 4 + 4 floats per tap
+    const bool l4dot = fuse_l4 && c.neck_res_blocks[MOGE_LEVELS - 1] == 0 && c.dims[4] == 32 && c.dims[3] == 64 && rs_is_phase(c.neck_resamplers[3]) &&
+                       rs_is_phase(c.head_resamplers[3]) && moge_tune_get("CONV_PP", 1) != 0;
     CHK(encode<T>(h, image, img_dtype, pl.H, pl.W, pl, st, !compose));
     // (the scale head runs behind the heads, see below)
-
-    // fp16 path, level 4 (no residual blocks there, 32 channels): out_k(x4_k + in4_k(n4)) = Wout_k x4_k + (Wout_k Win4_k) n4 + b2_k is evaluated
-    // INSIDE the two 64 -> 4 x 32 resampler convs (conv_pp.hip, fused output conv); head_final only resizes and remaps 4 + 4 floats per tap
     int nheads = 0;
     for (int k = 0; k < 3; k++) nheads += (c.heads & HEAD_BITS[k]) ? 1 : 0;
-    const bool l4dot = std::is_same<T, f16>::value && c.head_res_blocks[MOGE_LEVELS - 1] == 0 && c.neck_res_blocks[MOGE_LEVELS - 1] == 0 && c.dims[4] == 32 &&
-                       c.dims[3] == 64 && rs_is_phase(c.neck_resamplers[3]) && rs_is_phase(c.head_resamplers[3]) &&
-                       moge_tune_get("FUSE_L4", 1) != 0 && moge_tune_get("L4DOT", 1) != 0 && moge_tune_get("CONV_PP", 1) != 0;
     // small batches: the heads on their own streams and scratch triples (same kernels: bit-identical); not under the profiler, whose events bracket
     // launches on ONE stream.  HEAD_PIPE (default, round 6): every head on a side stream, level l of a head released by the event of neck level l;
     // HEAD_PIPE 0 (rounds 3-5): the first head on the caller's stream, the others forked behind the whole neck
@@ -1239,7 +1244,7 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
             UVTerm uvl = uv_term(A(h, S("neck.in%d.wu", l)), A(h, S("neck.in%d.wv", l)), Ww, Hh, aspect);
             if (rsl == MOGE_RS_CONV_TRANSPOSE) {
                 bool fused = false;
-                if (std::is_same<T, f16>::value && ct3_shape(ci, co))
+                if (fp16 && ct3_shape(ci, co))
                     CHK(convT_conv3_fused<T>(h, N[l - 1], P<T>(h, S("neck.rs%d.wc", l - 1)), P<T>(h, S("neck.rs%d.dw", l - 1)), A(h, S("neck.rs%d.bias_ct3", l - 1)), N[l], B,
                                              Hh / 2, Ww / 2, ci, co, &uvl, nullptr, nullptr, st, &fused));
                 if (!fused) {
@@ -1266,7 +1271,6 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
     }
     // ---- heads -------------------------------------------------------------------------------------------------------
     float* outs[3] = {o_points, o_normal, o_maskprob};
-    const bool fuse_l4 = std::is_same<T, f16>::value && c.head_res_blocks[MOGE_LEVELS - 1] == 0 && moge_tune_get("FUSE_L4", 1) != 0;
     hipStream_t st_main = st;
     int forked = 0;
     // Whatever way this function is left (a failed launch in the middle of a head included), the caller's stream must be ordered behind every
@@ -1307,7 +1311,6 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
             for (int i = 0; i < 3; i++) Sc[i] = (T*)(ws + pl.scratch[i]);
         }
         int cur = 0;                       // Sc[cur] holds the running x
-        const bool compose0 = compose && c.head_res_blocks[0] == 0 && c.head_resamplers[0] == MOGE_RS_CONV_TRANSPOSE;       // level 0 -> 1: ConvTranspose2d(input block(n0)) as one GEMM on n0
         if (!compose0) {
             CHK(conv1x1<T>(h, N[0], P<T>(h, name + ".in0.w"), M(h, name + ".input_blocks.0.bias"), Sc[cur], BP, c0, c0, nullptr, nullptr, cols, rows, st));
             CHK(res_blocks<T>(h, name, 0, c.head_res_blocks[0], Sc[cur], Sc[(cur + 1) % 3], B, rows, cols, c0, st, false, nullptr, Sc[(cur + 2) % 3], gn));
@@ -1320,8 +1323,7 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
             int nxt;
             bool in_fused = false;
             bool ct3_done = false;
-            if (rsl == MOGE_RS_CONV_TRANSPOSE && std::is_same<T, f16>::value && ct3_shape(ci, co) && !(l == 1 && compose0) && moge_tune_get("FUSE_IN", 1) != 0 &&
-                !(l == MOGE_LEVELS - 1 && fuse_l4)) {
+            if (fuse_in && rsl == MOGE_RS_CONV_TRANSPOSE && ct3_shape(ci, co) && !(l == 1 && compose0) && !(l == MOGE_LEVELS - 1 && fuse_l4)) {
                 // ConvTranspose2d + 3x3 + the head's `x + in_l(neck_l)` (modules.py:160-165, 245) in one composed conv: Sc[cur] (low-res) -> Sc[b2] (high-res)
                 CHK(convT_conv3_fused<T>(h, Sc[cur], P<T>(h, name + S(".rs%d.wc", l - 1)), P<T>(h, name + S(".rs%d.dw", l - 1)), A(h, name + S(".rs%d.bias_ct3", l - 1)), Sc[b2], B,
                                          Hh / 2, Ww / 2, ci, co, nullptr, N[l], P<T>(h, name + S(".in%d.w", l)), st, &ct3_done));
@@ -1339,8 +1341,7 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
                 const float* plain_bias = M(h, name + S(".resamplers.%d.%s.bias", l - 1, rs_final_conv(rsl)));
                 // resampler conv, with the head's `x + in_l(neck_l)` fused as a 1x1 side input when the halo kernel takes the shape
                 // (the first attempt passes the combined bias; if the shape is not eligible nothing ran and the plain form follows)
-                const bool try_fuse = std::is_same<T, f16>::value && rsl == MOGE_RS_CONV_TRANSPOSE && moge_tune_get("FUSE_IN", 1) != 0 && moge_tune_get("CONV_PP", 1) != 0 &&
-                                      !(l == MOGE_LEVELS - 1 && fuse_l4);
+                const bool try_fuse = fuse_in && rsl == MOGE_RS_CONV_TRANSPOSE && moge_tune_get("CONV_PP", 1) != 0 && !(l == MOGE_LEVELS - 1 && fuse_l4);
                 if (try_fuse) {
                     GemmArgs probe = gemm_args();
                     probe.a = Sc[a]; probe.H = Hh; probe.W = Ww; probe.C = co; probe.w = P<T>(h, name + S(".rs%d.w3", l - 1)); probe.ldw = 9 * co;
@@ -1409,7 +1410,7 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
     // remember buffers for debug taps
     h->last.valid = true; h->last.prec = TT<T>::PREC; h->last.B = B; h->last.rows = rows; h->last.cols = cols;
     h->last.bufs.clear();
-    if (std::is_same<T, f16>::value && h->half_resid && moge_tune_get("HALF_RESID", 1) != 0 && moge_tune_get("LN_FOLD", 1) != 0) h->last.bufs["x_final"] = {pl.xn, {(int64_t)BN * D, 1}};
+    if (fp16 && h->half_resid) h->last.bufs["x_final"] = {pl.xn, {(int64_t)BN * D, 1}};
     else h->last.bufs["x_final"] = {pl.x, {(int64_t)BN * D, 0}};
     h->last.bufs["tapcat"] = {pl.tapcat, {(int64_t)BP * c.n_taps * D, 1}};
     h->last.bufs["cls"] = {pl.cls, {(int64_t)B * D, 0}};
@@ -2017,14 +2018,13 @@ static int check_call(moge_handle* h, const void* image, int B, int H, int W, in
 }
 
 // number of sub-batches a batch of B runs as (each on its own internal stream): BATCH_SPLIT = 0/1 off, n >= 2 -> n parts (default 2) when
-// every part keeps at least BATCH_SPLIT_MIN = 3 images (batch 6 = 3 + 3: 211 -> 222 img/s; batch 4 = 2 + 2 falls into the latency-regime kernels: 215 -> 184)
+// every part keeps at least BATCH_SPLIT_MIN_PART = 3 images (batch 6 = 3 + 3: 211 -> 222 img/s; batch 4 = 2 + 2 falls into the latency-regime kernels: 215 -> 184)
+static constexpr int BATCH_SPLIT_MIN_PART = 3;
 static int split_parts(moge_handle* h, int B) {
     if (h->prof_on) return 1;
     int n = moge_tune_get("BATCH_SPLIT", 2);
     if (n > moge_handle::MAX_SPLIT) n = moge_handle::MAX_SPLIT;
-    int min_part = moge_tune_get("BATCH_SPLIT_MIN", 3);
-    if (min_part < 1) min_part = 1;                 // (a part of 0 images is not a batch)
-    while (n > 1 && B / n < min_part) n--;
+    while (n > 1 && B / n < BATCH_SPLIT_MIN_PART) n--;
     return n < 2 ? 1 : n;
 }
 // workspace bytes a forward over plan pl needs (callers size the arena BEFORE taking pointers into it)

@@ -299,7 +299,7 @@ def test_batch_split_streams_are_bit_identical(MoGeModel, tmp_path_factory):
         for half in (False, True):
             if half:
                 model.half()
-            for B in (9, 6, 7):                     # 4 + 5, 3 + 3 (the smallest parts BATCH_SPLIT_MIN allows), 3 + 4
+            for B in (9, 6, 7):                     # 4 + 5, 3 + 3 (the smallest parts split_parts allows), 3 + 4
                 x = torch.rand(B, 3, 84, 112, generator=torch.Generator().manual_seed(3 + B))
                 L.tune("BATCH_SPLIT", 0)
                 ref = model.infer(x, num_tokens=108)
