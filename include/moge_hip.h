@@ -338,6 +338,43 @@ int moge_test_posembed(const float* pos, float* out, int D, int rows, int cols, 
 /* focal/shift solve on (B,H,W,3) points + (B,H,W) 0/1 mask; focal_in NULL or (B,) */
 int moge_test_recover(const float* points, const uint8_t* mask, const float* focal_in, int B, int H, int W,
                       float* focal, float* shift, int32_t* status, void* stream);
+/* The decoder tail (post.hip), as the model dispatches it: out = activation(resize(conv(x) [+ w2 . n4] + bias)) with the 1x1 (ksize 1, modules.py:231)
+ * or 3x3 replicate-padded (ksize 3, v1.py:108: weights (CO,C,3,3), dense x, no n4) output conv at (Hd,Wd) and the bilinear resize to (H,W) (v2.py:170).
+ * kind 0 points (3 channels, `remap` = moge_remap), 1 normal (unit vector, norm clamped at 1e-12), 2 mask (sigmoid), 3 raw single channel.
+ * x (B,Hd,Wd,ld) fp32, rounded to `precision` storage; channels [choff, choff + C) are the kernel's input (a slice of a wider map); w (CO,C), bias (CO).
+ * n4 (same shape, optional) with weights w2 (CO,C) lives in ONE allocation with x: above it (n4_below 0) or below it (n4_below 1).
+ * fp16 with C == 32 runs head_final32_kernel, every other case the generic kernels.  out (B,H,W,CO) fp32. */
+typedef struct moge_test_head_args {
+    int32_t precision, kind, remap, ksize;
+    int32_t B, Hd, Wd, C, ld, choff, H, W;
+    int32_t n4_below;
+    const float* x; const float* w; const float* bias;
+    const float* n4; const float* w2;
+    float* out;
+} moge_test_head_args;
+int moge_test_head_final(const moge_test_head_args* args, void* stream);
+/* head_final on the maps of the fused output conv: out = activation(resize(y [+ z[..., zoff:zoff+4]]) + bias); y (B,Hd,Wd,4) fp32, z (B,Hd,Wd,zld) fp32 or
+ * NULL (zld, zoff multiples of 4); lane 3 of a tap is ignored by the 3-channel kinds */
+int moge_test_head_final_dot(int kind, int remap, const float* y, const float* z, int zld, int zoff, const float* bias, float* out, int B, int Hd, int Wd,
+                             int H, int W, void* stream);
+/* scale head layer (modules.py:184-192): out (B,N) = act(in (B,K) W (N,K)^T + bias); act 0 none 1 relu 2 exp; K % 4 == 0 */
+int moge_test_mlp_layer(const float* in, const float* W, const float* bias, float* out, int B, int K, int N, int act, void* stream);
+/* LayerNorm (eps 1e-6) through every output mode of layernorm_kernel.  y is IN / OUT: the caller pre-fills it and the kernel writes only its own
+ * columns.  plain: y (rows, ldo), columns [coloff, coloff + D).  tap_mode (rows = B Ntok): token 0 -> cls_out (B, D) fp32 (NULL: not written), token
+ * t > 0 -> y ((B (Ntok - 1)), ldo) row b (Ntok - 1) + t - 1.  stream16 (precision MOGE_FP16 only): x is rounded to fp16 and read by launch_layernorm_x16. */
+int moge_test_layernorm_ex(int precision, int stream16, const float* x, const float* w, const float* b, float* y, float* cls_out, int rows, int D, int ldo,
+                           int coloff, int tap_mode, int Ntok, void* stream);
+/* LayerNorm folded into the consumer GEMM (fp16 path): ln_raw -> fp16 copy of x (rows, D) returned as fp32 + mr (rows, 2) = (mean, rstd);
+ * ln_finalize: part (rows, NP, 2) = (sum, sum of squares) partials -> mr; fold_ln: W (N,K), g / beta (K), b (N) -> Wf = fp16(g W) returned as fp32,
+ * c (N) = row sums of the ROUNDED Wf, bf (N) = b + W beta */
+int moge_test_ln_raw(const float* x, float* x16_out, float* mr, int rows, int D, void* stream);
+int moge_test_ln_finalize(const float* part, float* mr, int rows, int NP, int D, void* stream);
+int moge_test_fold_ln(const float* W, const float* g, const float* beta, const float* b, float* Wf_out, float* c, float* bf, int N, int K, void* stream);
+/* v1.py:127-130: bilinear resize of x (B,hs,ws,C) to (B,OH,OW,Cp) with u = linspace(u0,u1,OW), v = linspace(v0,v1,OH) in channels C, C + 1 and zeros above */
+int moge_test_resize_bilinear_uv(int precision, const float* x, float* out, int B, int hs, int ws, int C, int OH, int OW, int Cp, float u0, float u1,
+                                 float v0, float v1, void* stream);
+/* scripts/infer.py:98: uint8 (B,H,W,3) -> (B,3,H,W) = image / 255 in `precision` storage, returned as fp32 */
+int moge_test_u8_ingest(int precision, const uint8_t* in, float* out, int B, int H, int W, void* stream);
 
 /* ---- optimal-alignment solvers of the evaluation path (reference: moge/utils/alignment.py, called by moge/test/metrics.py:128-282) -------
  * Stateless (no handle); every pointer is device memory; results are written asynchronously on `stream`.

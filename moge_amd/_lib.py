@@ -85,6 +85,13 @@ class TestCt3Args(C.Structure):
                 ("wu", C.c_void_p), ("wv", C.c_void_p), ("u0", C.c_float), ("u1", C.c_float), ("v0", C.c_float), ("v1", C.c_float), ("y", C.c_void_p)]
 
 
+class TestHeadArgs(C.Structure):
+    """moge_test_head_args (tests only): the decoder tail - output conv + bilinear resize + remap / normalise / sigmoid."""
+    _fields_ = [("precision", C.c_int32), ("kind", C.c_int32), ("remap", C.c_int32), ("ksize", C.c_int32),
+                ("B", C.c_int32), ("Hd", C.c_int32), ("Wd", C.c_int32), ("C", C.c_int32), ("ld", C.c_int32), ("choff", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("n4_below", C.c_int32), ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("n4", C.c_void_p), ("w2", C.c_void_p), ("out", C.c_void_p)]
+
+
 class MogeError(RuntimeError):
     pass
 
@@ -135,6 +142,15 @@ def _load(path: str = LIB_PATH, mode: int = C.RTLD_GLOBAL) -> C.CDLL:
         "moge_test_norm_act": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),
         "moge_test_posembed": (C.c_int, [f32p, f32p, i32, i32, i32, vp]),
         "moge_test_recover": (C.c_int, [f32p, vp, f32p, i32, i32, i32, f32p, f32p, vp, vp]),
+        "moge_test_head_final": (C.c_int, [C.POINTER(TestHeadArgs), vp]),
+        "moge_test_head_final_dot": (C.c_int, [i32, i32, f32p, f32p, i32, i32, f32p, f32p, i32, i32, i32, i32, i32, vp]),
+        "moge_test_mlp_layer": (C.c_int, [f32p, f32p, f32p, f32p, i32, i32, i32, i32, vp]),
+        "moge_test_layernorm_ex": (C.c_int, [i32, i32, f32p, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, vp]),
+        "moge_test_ln_raw": (C.c_int, [f32p, f32p, f32p, i32, i32, vp]),
+        "moge_test_ln_finalize": (C.c_int, [f32p, f32p, i32, i32, i32, vp]),
+        "moge_test_fold_ln": (C.c_int, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, vp]),
+        "moge_test_resize_bilinear_uv": (C.c_int, [i32, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
+        "moge_test_u8_ingest": (C.c_int, [i32, vp, f32p, i32, i32, i32, vp]),
         "moge_align_l1": (C.c_int, [f32p, f32p, f32p, i32, i32, C.c_float, f32p, f32p, vp, vp]),
         "moge_align_l1_anchored": (C.c_int, [f32p, f32p, f32p, i32, i32, i32, vp, vp, i32, C.c_float, f32p, f32p, vp, vp]),
         "moge_align_trunc_workspace": (C.c_int, [i32, i32, C.POINTER(i64)]),
@@ -182,6 +198,8 @@ EXPORTS = ["moge_abi_version", "moge_last_error", "moge_create", "moge_create_v1
            "moge_postprocess", "moge_depth_edge_mask", "moge_cast_f16", "moge_sync", "moge_profile_enable", "moge_profile_read", "moge_debug_tap", "moge_tune_set", "moge_test_gemm",
            "moge_test_gemm_ex", "moge_test_layernorm", "moge_test_attention", "moge_test_conv3x3", "moge_test_conv_ex", "moge_test_convt2x2", "moge_test_ct3", "moge_test_preprocess",
            "moge_test_resize_bicubic_aa", "moge_test_groupnorm_relu", "moge_test_norm_act", "moge_test_posembed", "moge_test_recover",
+           "moge_test_head_final", "moge_test_head_final_dot", "moge_test_mlp_layer", "moge_test_layernorm_ex", "moge_test_ln_raw", "moge_test_ln_finalize",
+           "moge_test_fold_ln", "moge_test_resize_bilinear_uv", "moge_test_u8_ingest",
            "moge_align_l1", "moge_align_l1_anchored", "moge_align_trunc_workspace", "moge_align_trunc", "moge_align_trunc_anchored",
            "moge_align_select", "moge_align_lstsq",
            "moge_metrics_lr_sample", "moge_metrics_error", "moge_metrics_masked_max", "moge_metrics_boundary", "moge_metrics_segment_stats",

@@ -322,7 +322,155 @@ static int t_ct3(const moge_test_ct3_args& a, hipStream_t st) {
     return 0;
 }
 
+// The decoder tail (post.hip): 1x1 / 3x3 output conv + bilinear resize + remap through launch_head_final / launch_head_final_k3 as the model calls
+// them.  x and the optional second input n4 share ONE allocation (the kernel reaches n4 through the pointer difference n4 - x4), in either order.
+template <typename T>
+static int t_head_final(const moge_test_head_args& a, hipStream_t st) {
+    const int CH = TT<T>::CH;
+    if (a.choff % CH) return MOGE_ERR_INVALID;                               // the slice must start on a 16-byte chunk
+    if (a.ksize == 3 && (a.n4 || a.ld != a.C || a.choff)) return MOGE_ERR_INVALID;      // the 3x3 form takes one dense map
+    const size_t n = (size_t)a.B * a.Hd * a.Wd * a.ld;
+    DevBuf buf;
+    TCHK(buf.alloc((a.n4 ? 2 : 1) * n * sizeof(T)));
+    T* xb = (T*)buf.p + (a.n4 && a.n4_below ? n : 0);
+    T* nb = a.n4 ? (T*)buf.p + (a.n4_below ? 0 : n) : nullptr;
+    TL(to_t<T>(a.x, xb, (long)n, st));
+    if (nb) TL(to_t<T>(a.n4, nb, (long)n, st));
+    if (a.ksize == 3) TL(launch_head_final_k3<T>(a.kind, xb, a.w, a.bias, a.out, a.B, a.Hd, a.Wd, a.C, a.H, a.W, a.remap, st));
+    else TL(launch_head_final<T>(a.kind, xb + a.choff, a.w, a.bias, nb ? nb + a.choff : nullptr, a.w2, a.out, a.B, a.Hd, a.Wd, a.C, a.H, a.W, a.remap, st, a.ld));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <typename T>
+static int t_layernorm_ex(int stream16, const float* x, const float* w, const float* b, float* y, float* cls_out, long rows, int D, int ldo, int coloff,
+                          int tap_mode, int Ntok, hipStream_t st) {
+    const long orows = tap_mode ? rows / Ntok * (Ntok - 1) : rows;
+    const long ny = orows * ldo;
+    DevBuf xb, yb;
+    void* yp = y;
+    if (std::is_same<T, f16>::value) {                   // the caller's pre-filled output, rounded to the storage type
+        TCHK(yb.alloc((size_t)ny * sizeof(f16)));
+        TL((launch_convert<float, f16>(y, yb.p, ny, st)));
+        yp = yb.p;
+    }
+    if (stream16) {
+        TCHK(xb.alloc((size_t)rows * D * sizeof(f16)));
+        TL((launch_convert<float, f16>(x, xb.p, rows * D, st)));
+        TL(launch_layernorm_x16(xb.p, w, b, yp, cls_out, rows, D, ldo, coloff, tap_mode, Ntok, st));
+    } else {
+        TL(launch_layernorm<T>(x, w, b, yp, cls_out, rows, D, ldo, coloff, tap_mode, Ntok, st));
+    }
+    if (std::is_same<T, f16>::value) TL((launch_convert<f16, float>(yb.p, y, ny, st)));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <typename T>
+static int t_resize_bilinear_uv(const float* x, float* out, int B, int hs, int ws, int C, int OH, int OW, int Cp, float u0, float u1, float v0, float v1,
+                                hipStream_t st) {
+    const size_t nx = (size_t)B * hs * ws * C, ny = (size_t)B * OH * OW * Cp;
+    DevBuf xb, yb;
+    TCHK(xb.alloc(nx * sizeof(T))); TCHK(yb.alloc(ny * sizeof(T)));
+    TL(to_t<T>(x, xb.p, (long)nx, st));
+    TL(launch_resize_bilinear_uv<T>(xb.p, yb.p, B, hs, ws, C, OH, OW, Cp, u0, u1, v0, v1, st));
+    TL(from_t<T>(yb.p, out, (long)ny, st));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <typename T>
+static int t_u8_ingest(const uint8_t* in, float* out, int B, int H, int W, hipStream_t st) {
+    const size_t n = (size_t)B * 3 * H * W;
+    DevBuf yb;
+    TCHK(yb.alloc(n * sizeof(T)));
+    TL(launch_u8hwc_to_chw<T>(in, yb.p, B, H, W, st));
+    TL(from_t<T>(yb.p, out, (long)n, st));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" {
+
+int moge_test_head_final(const moge_test_head_args* a, void* stream) {
+    if (!a || !a->x || !a->w || !a->bias || !a->out || (a->n4 && !a->w2)) return MOGE_ERR_INVALID;
+    if (a->kind < 0 || a->kind > 3 || a->remap < 0 || a->remap > 3 || (a->ksize != 1 && a->ksize != 3)) return MOGE_ERR_INVALID;
+    if (a->B < 1 || a->Hd < 1 || a->Wd < 1 || a->H < 1 || a->W < 1 || a->C < 1 || a->choff < 0 || a->ld < a->choff + a->C) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    return a->precision == MOGE_FP16 ? t_head_final<f16>(*a, st) : t_head_final<float>(*a, st);
+}
+
+int moge_test_head_final_dot(int kind, int remap, const float* y, const float* z, int zld, int zoff, const float* bias, float* out, int B, int Hd, int Wd,
+                             int H, int W, void* stream) {
+    if (!y || !bias || !out || kind < 0 || kind > 3 || remap < 0 || remap > 3 || B < 1 || Hd < 1 || Wd < 1 || H < 1 || W < 1) return MOGE_ERR_INVALID;
+    if (z && (zld < 4 || (zld & 3) || zoff < 0 || (zoff & 3) || zoff + 4 > zld)) return MOGE_ERR_INVALID;      // 16-byte taps
+    hipStream_t st = (hipStream_t)stream;
+    TL(launch_head_final_dot(kind, y, z, zld, zoff, bias, out, B, Hd, Wd, H, W, remap, st));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int moge_test_mlp_layer(const float* in, const float* W, const float* bias, float* out, int B, int K, int N, int act, void* stream) {
+    if (!in || !W || !bias || !out || B < 1 || K < 1 || N < 1 || act < 0 || act > 2) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    TL(launch_mlp_layer(in, W, bias, out, B, K, N, act, st));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int moge_test_layernorm_ex(int precision, int stream16, const float* x, const float* w, const float* b, float* y, float* cls_out, int rows, int D, int ldo,
+                           int coloff, int tap_mode, int Ntok, void* stream) {
+    if (!x || !w || !b || !y || rows < 1 || D < 1 || coloff < 0 || ldo < coloff + D) return MOGE_ERR_INVALID;
+    if (stream16 && precision != MOGE_FP16) return MOGE_ERR_INVALID;          // the fp16 stream writes fp16
+    if (tap_mode && (Ntok < 2 || rows % Ntok)) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    return precision == MOGE_FP16 ? t_layernorm_ex<f16>(stream16, x, w, b, y, cls_out, rows, D, ldo, coloff, tap_mode, Ntok, st)
+                                  : t_layernorm_ex<float>(0, x, w, b, y, cls_out, rows, D, ldo, coloff, tap_mode, Ntok, st);
+}
+
+int moge_test_ln_raw(const float* x, float* x16_out, float* mr, int rows, int D, void* stream) {
+    if (!x || !x16_out || !mr || rows < 1 || D < 1) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf ob;
+    TCHK(ob.alloc((size_t)rows * D * sizeof(f16)));
+    TL(launch_ln_raw<f16>(x, ob.p, mr, rows, D, st));
+    TL((launch_convert<f16, float>(ob.p, x16_out, (long)rows * D, st)));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int moge_test_ln_finalize(const float* part, float* mr, int rows, int NP, int D, void* stream) {
+    if (!part || !mr || rows < 1 || NP < 1 || D < 1) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    TL(launch_ln_finalize(part, mr, rows, NP, D, st));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int moge_test_fold_ln(const float* W, const float* g, const float* beta, const float* b, float* Wf_out, float* c, float* bf, int N, int K, void* stream) {
+    if (!W || !g || !beta || !b || !Wf_out || !c || !bf || N < 1 || K < 1) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf wf;
+    TCHK(wf.alloc((size_t)N * K * sizeof(f16)));
+    TL(launch_fold_ln<f16>(W, g, beta, b, wf.p, c, bf, N, K, st));
+    TL((launch_convert<f16, float>(wf.p, Wf_out, (long)N * K, st)));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int moge_test_resize_bilinear_uv(int precision, const float* x, float* out, int B, int hs, int ws, int C, int OH, int OW, int Cp, float u0, float u1,
+                                 float v0, float v1, void* stream) {
+    if (!x || !out || B < 1 || hs < 1 || ws < 1 || C < 1 || OH < 1 || OW < 1) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    return precision == MOGE_FP16 ? t_resize_bilinear_uv<f16>(x, out, B, hs, ws, C, OH, OW, Cp, u0, u1, v0, v1, st)
+                                  : t_resize_bilinear_uv<float>(x, out, B, hs, ws, C, OH, OW, Cp, u0, u1, v0, v1, st);
+}
+
+int moge_test_u8_ingest(int precision, const uint8_t* in, float* out, int B, int H, int W, void* stream) {
+    if (!in || !out || B < 1 || H < 1 || W < 1) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    return precision == MOGE_FP16 ? t_u8_ingest<f16>(in, out, B, H, W, st) : t_u8_ingest<float>(in, out, B, H, W, st);
+}
 
 int moge_test_ct3(const moge_test_ct3_args* args, void* stream) {
     if (!args || args->precision != MOGE_FP16) return MOGE_ERR_INVALID;

@@ -246,3 +246,120 @@ def ct3(x_nhwc, wt, bt, w3, b3, side=None, side_w=None, uv=None, no_border=False
     a.y = y.data_ptr()
     L.check(L.lib.moge_test_ct3(C.byref(a), st()))
     return y
+
+
+def head_final(prec, kind, x, w, bias, H, W, remap=0, ksize=1, C=None, choff=0, n4=None, w2=None, n4_below=False, raw=False):
+    """The decoder tail (moge_test_head_final): x (B,Hd,Wd,ld) with channels [choff, choff + C) the kernel's input, w (CO,C) or (CO,C,3,3).
+    raw=True returns the status code instead of raising."""
+    import ctypes as C_
+    x, w, bias = _f(x), _f(w), _f(bias)
+    B, Hd, Wd, ld = x.shape
+    Cc = ld if C is None else C
+    CO = 3 if kind in (0, 1) else 1
+    out = torch.empty((B, H, W, CO), device="cuda", dtype=torch.float32)
+    a = L.TestHeadArgs()
+    a.precision, a.kind, a.remap, a.ksize = prec, kind, remap, ksize
+    a.B, a.Hd, a.Wd, a.C, a.ld, a.choff, a.H, a.W = B, Hd, Wd, Cc, ld, choff, H, W
+    a.n4_below = int(bool(n4_below))
+    a.x, a.w, a.bias, a.out = x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr()
+    keep = []
+    if n4 is not None:
+        keep += [_f(n4), _f(w2)]
+        a.n4, a.w2 = keep[0].data_ptr(), keep[1].data_ptr()
+    rc = L.lib.moge_test_head_final(C_.byref(a), st())
+    if raw:
+        return rc
+    L.check(rc)
+    return out
+
+
+def head_final_dot(kind, y, bias, H, W, remap=0, z=None, zoff=0, raw=False):
+    y, bias = _f(y), _f(bias)
+    z = None if z is None else _f(z)
+    B, Hd, Wd, _ = y.shape
+    CO = 3 if kind in (0, 1) else 1
+    out = torch.empty((B, H, W, CO), device="cuda", dtype=torch.float32)
+    rc = L.lib.moge_test_head_final_dot(kind, remap, _p(y), _p(z), 0 if z is None else z.shape[-1], zoff, _p(bias), _p(out), B, Hd, Wd, H, W, st())
+    if raw:
+        return rc
+    L.check(rc)
+    return out
+
+
+def mlp_layer(x, W, bias, act, raw=False):
+    x, W, bias = _f(x), _f(W), _f(bias)
+    B, K = x.shape
+    N = W.shape[0]
+    out = torch.empty((B, N), device="cuda", dtype=torch.float32)
+    rc = L.lib.moge_test_mlp_layer(_p(x), _p(W), _p(bias), _p(out), B, K, N, act, st())
+    if raw:
+        return rc
+    L.check(rc)
+    return out
+
+
+def layernorm_ex(prec, x, w, b, y_prefill, stream16=False, coloff=0, tap_mode=False, Ntok=0, cls_prefill=None, raw=False):
+    """LayerNorm through the output modes of layernorm_kernel (moge_test_layernorm_ex): y_prefill (out rows, ldo) and cls_prefill (B, D) or None are
+    copied, handed to the kernel and returned, so that what the kernel left alone can be checked."""
+    x, w, b = _f(x), _f(w), _f(b)
+    y = _f(y_prefill).clone()
+    cls = None if cls_prefill is None else _f(cls_prefill).clone()
+    rows, D = x.shape
+    rc = L.lib.moge_test_layernorm_ex(prec, int(bool(stream16)), _p(x), _p(w), _p(b), _p(y), _p(cls), rows, D, y.shape[-1], coloff, int(bool(tap_mode)), Ntok, st())
+    if raw:
+        return rc
+    L.check(rc)
+    return y, cls
+
+
+def ln_raw(x, raw=False):
+    x = _f(x)
+    rows, D = x.shape
+    x16 = torch.empty_like(x)
+    mr = torch.empty((rows, 2), device="cuda", dtype=torch.float32)
+    rc = L.lib.moge_test_ln_raw(_p(x), _p(x16), _p(mr), rows, D, st())
+    if raw:
+        return rc
+    L.check(rc)
+    return x16, mr
+
+
+def ln_finalize(part, D, raw=False):
+    part = _f(part)
+    rows, NP, _ = part.shape
+    mr = torch.empty((rows, 2), device="cuda", dtype=torch.float32)
+    rc = L.lib.moge_test_ln_finalize(_p(part), _p(mr), rows, NP, D, st())
+    if raw:
+        return rc
+    L.check(rc)
+    return mr
+
+
+def fold_ln(W, g, beta, b):
+    W, g, beta, b = _f(W), _f(g), _f(beta), _f(b)
+    N, K = W.shape
+    Wf = torch.empty_like(W)
+    c = torch.empty((N,), device="cuda", dtype=torch.float32)
+    bf = torch.empty((N,), device="cuda", dtype=torch.float32)
+    L.check(L.lib.moge_test_fold_ln(_p(W), _p(g), _p(beta), _p(b), _p(Wf), _p(c), _p(bf), N, K, st()))
+    return Wf, c, bf
+
+
+def resize_bilinear_uv(prec, x, OH, OW, Cp, uv_range, raw=False):
+    x = _f(x)
+    B, hs, ws, Cc = x.shape
+    out = torch.empty((B, OH, OW, Cp), device="cuda", dtype=torch.float32)
+    u0, u1, v0, v1 = uv_range
+    rc = L.lib.moge_test_resize_bilinear_uv(prec, _p(x), _p(out), B, hs, ws, Cc, OH, OW, Cp, u0, u1, v0, v1, st())
+    if raw:
+        return rc
+    L.check(rc)
+    return out
+
+
+def u8_ingest(prec, img_u8):
+    img = img_u8.to("cuda", torch.uint8).contiguous()
+    B, H, W, _ = img.shape
+    out = torch.empty((B, 3, H, W), device="cuda", dtype=torch.float32)
+    L.check(L.lib.moge_test_u8_ingest(prec, _p(img), _p(out), B, H, W, st()))
+    return out
