@@ -465,6 +465,18 @@ int moge_eval_quantile_cut(float* depth, uint8_t* mask, int n, float q, float dr
  * (HOST pointer, 9 floats) = inv(tgt_intrinsics) */
 int moge_eval_unproject(float* depth, uint8_t* mask, int out_h, int out_w, const float* kinv, const int32_t* count, float* points, void* stream);
 
+/* ---- normal-guided depth refinement (reference: moge/utils/geometry_torch.py:206-233 refine_depth_with_normal; python mirror
+ * moge_amd/refine.py) ----------------------------------------------------------------------------------------------
+ * Stateless (no handle); every pointer is device memory; the result is written asynchronously on `stream`.
+ * depth (B, H, W), normal (B, H, W, 3), intrinsics (B, 3, 3) normalised (uv at pixel centres in [0, 1]), out (B, H, W), all fp32; mask (B, H, W)
+ * u8 or NULL.  kernel_size 3, 5 or 7 with H, W >= kernel_size, iterations >= 0: otherwise MOGE_ERR_INVALID, as for a NULL required pointer.
+ * With a mask, masked-out pixels take no part (as taps or as centres) and come back as the bits of their input depth; NULL is the reference's
+ * formula.  depth is not written.  workspace: moge_refine_depth_workspace(B, H, W) bytes (four fp32 planes per image).  Two calls give the same
+ * bits, and an image gives the same bits alone as inside a batch. */
+int moge_refine_depth_workspace(int B, int H, int W, int64_t* bytes);
+int moge_refine_depth(const float* depth, const float* normal, const float* intrinsics, const uint8_t* mask, int B, int H, int W, int kernel_size,
+                      int iterations, float damp, float eps, void* workspace, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,8 @@ def _load(path: str = LIB_PATH, mode: int = C.RTLD_GLOBAL) -> C.CDLL:
         "moge_eval_remap": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp]),
         "moge_eval_quantile_cut": (C.c_int, [vp, vp, i32, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp]),
         "moge_eval_unproject": (C.c_int, [vp, vp, i32, i32, f32p, vp, vp, vp]),
+        "moge_refine_depth_workspace": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
+        "moge_refine_depth": (C.c_int, [f32p, f32p, f32p, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, f32p, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so does not export what the header declares
@@ -205,7 +207,8 @@ EXPORTS = ["moge_abi_version", "moge_last_error", "moge_create", "moge_create_v1
            "moge_metrics_lr_sample", "moge_metrics_error", "moge_metrics_masked_max", "moge_metrics_boundary", "moge_metrics_segment_stats",
            "moge_metrics_segment_pack", "moge_metrics_segment_error",
            "moge_eval_lanczos_workspace", "moge_eval_lanczos", "moge_eval_masked_nearest", "moge_eval_resize_nearest", "moge_eval_remap",
-           "moge_eval_quantile_cut", "moge_eval_unproject"]
+           "moge_eval_quantile_cut", "moge_eval_unproject",
+           "moge_refine_depth_workspace", "moge_refine_depth"]
 
 
 def check(code: int) -> None:

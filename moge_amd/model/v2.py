@@ -506,6 +506,27 @@ class MoGeModel:
                                                out.data_ptr(), L.stream_ptr(self._device)))
         return out[0] if squeeze else out
 
+    @torch.inference_mode()
+    def refine_depth(self, output: Dict[str, torch.Tensor], iterations: int = 10, **kw) -> Dict[str, torch.Tensor]:
+        """Feed the normal map back into the geometry: `moge_amd.refine.refine_depth_with_normal` on an `infer()` output (batched or not), with
+        mask = output["mask"] (or isfinite(depth) when the model has no mask head).  Returns a shallow copy with `depth` replaced and `points`
+        rescaled by depth_refined / depth where the mask holds and depth > 0 (exact for a pinhole point map); other entries are left as they are.
+        **kw: damp, eps, kernel_size of refine_depth_with_normal.  ValueError if the output has no `normal` (a config without the normal head)."""
+        from ..refine import refine_depth_with_normal
+        if "normal" not in output:
+            raise ValueError("refine_depth needs the normal map: this output has no 'normal' (the model has no normal head)")
+        if "depth" not in output or "intrinsics" not in output:
+            raise ValueError("refine_depth needs 'depth' and 'intrinsics' in the output (the points head)")
+        depth = output["depth"]
+        mask = output["mask"] if "mask" in output else torch.isfinite(depth)
+        refined = refine_depth_with_normal(depth, output["normal"], output["intrinsics"], iterations=iterations, mask=mask, **kw)
+        res = dict(output)
+        res["depth"] = refined
+        if "points" in output:
+            scaled = mask & (depth > 0)             # a masked-in depth of 0 (the kernel clamps it to eps) has no ratio: its point stays
+            res["points"] = torch.where(scaled[..., None], output["points"] * (refined / depth)[..., None], output["points"])
+        return res
+
     def _infer_device(self, image, img_dtype, B, H, W, omit_batch_dim, num_tokens, resolution_level, force_projection, apply_mask, fov_x, use_fp16):
         if num_tokens is None:
             min_tokens, max_tokens = self.num_tokens_range
