@@ -268,10 +268,16 @@ int moge_test_gemm(int precision, const float* A, const float* W, const float* b
  *                  xres == NULL: the fp16 residual stream of a `.half()` model - x16_out is IN / OUT (fp32 values, rounded to fp16 on the
  *                  way in): x16 <- fp16(x16 + gamma (acc + bias)); ln_part_out (optional) = the statistics of the ROUNDED row
  *   MOGE_TG_QKV    q/k/v_out (B,nh,Ntok,64) = head-major split of lnfold(acc) + bias, q scaled by qscale          attention.py:72-74
+ *                  v_transposed: v_out is (B,nh,64,Npad), Npad = Ntok rounded up to 64 - the V^T of the fp32 path - and IN / OUT: the caller
+ *                  pre-fills it, the epilogue must leave the key padding [Ntok, Npad) alone
  *   MOGE_TG_CONVT  out (B,2 pixH,2 pixW,Cout): n = (dy*2+dx)*Cout + co of pixel m = (b*pixH + y)*pixW + x goes to (2y+dy, 2x+dx)   modules.py:162
+ *                  wu != NULL: + wu[co] u + wv[co] v at the OUTPUT pixel (linspace over 2 pixW / 2 pixH), or with uv_in + wu[n] u + wv[n] v at the
+ *                  INPUT pixel (linspace over pixW / pixH; wu, wv have N = 4 Cout entries): the uv channels of MoGe-1's ConvTranspose2d, v1.py:118-121
+ *   MOGE_TG_PATCH  xres (B Ntok, N) IN / OUT, M = B Np: row b Ntok + 1 + p = acc + bias + pos[1 + p]; cls != NULL: row b Ntok = cls + pos[0]
+ *                  (patch_embed.py:75, vision_transformer.py:228-231); pos (1 + Np, N); every other row keeps the caller's fill
  * lnfold(acc) = ln_mr[m][1] * (acc - ln_mr[m][0] * ln_c[n]) when ln_mr != NULL (LayerNorm folded into the consumer GEMM), else acc.
  * u(x) = linspace(u0,u1,pixW)[m % pixW], v(y) = linspace(v0,v1,pixH)[(m / pixW) % pixH] when wu != NULL. */
-enum { MOGE_TG_STORE = 0, MOGE_TG_RESID = 1, MOGE_TG_QKV = 2, MOGE_TG_CONVT = 3 };
+enum { MOGE_TG_STORE = 0, MOGE_TG_RESID = 1, MOGE_TG_QKV = 2, MOGE_TG_CONVT = 3, MOGE_TG_PATCH = 4 };
 typedef struct moge_test_gemm_args {
     int32_t precision, kind, act;            /* act: 0 none 1 relu 2 gelu (STORE only) */
     int32_t M, N, K;
@@ -282,6 +288,9 @@ typedef struct moge_test_gemm_args {
     int32_t pixW, pixH, Cout;
     float* xres; const float* gamma; float* x16_out; float* ln_part_out;      /* RESID */
     float* q_out; float* k_out; float* v_out; int32_t nh, Ntok; float qscale; /* QKV: M = B*Ntok, N = 3*nh*64 */
+    const float* pos; const float* cls; int32_t Np;                           /* PATCH (with xres and Ntok) */
+    int32_t v_transposed;                                                     /* QKV */
+    int32_t uv_in;                                                            /* CONVT */
 } moge_test_gemm_args;
 int moge_test_gemm_ex(const moge_test_gemm_args* args, void* stream);
 /* LayerNorm rows of x[rows, D], eps 1e-6 */
@@ -326,8 +335,17 @@ int moge_test_convt2x2(int precision, const float* x, const float* w, const floa
                        int Cin, int Cout, void* stream);
 /* image (B,3,H,W) fp32 -> antialiased bilinear resize to (14*rows,14*cols), normalised, NCHW fp32 */
 int moge_test_preprocess(const float* image, float* out, int B, int H, int W, int rows, int cols, void* stream);
+/* launch_preprocess with the arguments the model gives it: the image (fp32 values) is read as fp32 or rounded to fp16 (in_fp16), the output is fp32 or fp16
+ * storage (out_fp16).  nchw_out 0: `out` is the im2col matrix (B rows cols, ldk), patch row (py cols + px), column c 196 + iy 14 + ix, columns [588, ldk)
+ * zeroed by the kernel; nchw_out 1: (B,3,14 rows,14 cols).  `out` is IN / OUT fp32: the caller's pre-fill is converted to the storage type, the whole
+ * buffer comes back.  round16 (fp32 image only): values rounded to fp16 on load; aa 0: the two-tap bilinear of onnx_compatible_mode.  zero_i32: the
+ * caller's int32 device buffer whose first zero_n entries the kernel zeroes (NULL with zero_n 0: none).  What the launcher rejects is MOGE_ERR_INVALID. */
+int moge_test_preprocess_ex(int in_fp16, int out_fp16, const float* image, float* out, int32_t* zero_i32, int B, int H, int W, int rows, int cols, int ldk,
+                            int nchw_out, int round16, int aa, int zero_n, void* stream);
 /* MoGe-1 kernels: image (B,3,H,W) fp32 -> bicubic antialiased resize (OH,OW), NCHW fp32 (v1.py:275) */
 int moge_test_resize_bicubic_aa(const float* image, float* out, int B, int H, int W, int OH, int OW, void* stream);
+/* ... with the image rounded to fp16 and read by the <f16> kernel (in_fp16), and round16: values rounded to fp16 on load AND on store (a .half() model) */
+int moge_test_resize_bicubic_aa_ex(int in_fp16, const float* image, float* out, int B, int H, int W, int OH, int OW, int round16, void* stream);
 /* relu(GroupNorm(groups, C)(x)), eps 1e-5, NHWC x (B,H,W,C) fp32 in / out, computed in `precision` (v1.py:44-49) */
 int moge_test_groupnorm_relu(int precision, const float* x, const float* gamma, const float* beta, float* y, int B, int H, int W, int C, int groups, void* stream);
 /* act(norm(x)) of a v2 residual block (modules.py:31-58): groups = 0 no norm, 1 "layer_norm", C / 32 "group_norm", C "instance_norm" (gamma = beta = NULL);
@@ -335,6 +353,8 @@ int moge_test_groupnorm_relu(int precision, const float* x, const float* gamma, 
 int moge_test_norm_act(int precision, const float* x, const float* gamma, const float* beta, float* y, int B, int H, int W, int C, int groups, int act, int in_place, void* stream);
 /* pos_embed (1+37*37, D) -> (1+rows*cols, D) bicubic with the +0.1 kludge */
 int moge_test_posembed(const float* pos, float* out, int D, int rows, int cols, void* stream);
+/* ... size_mode 1: onnx_compatible_mode - resampled by output size (source scale 37 / n), never bypassed (vision_transformer.py:192,202-210) */
+int moge_test_posembed_ex(const float* pos, float* out, int D, int rows, int cols, int size_mode, void* stream);
 /* focal/shift solve on (B,H,W,3) points + (B,H,W) 0/1 mask; focal_in NULL or (B,) */
 int moge_test_recover(const float* points, const uint8_t* mask, const float* focal_in, int B, int H, int W,
                       float* focal, float* shift, int32_t* status, void* stream);

@@ -66,7 +66,8 @@ class TestGemmArgs(C.Structure):
                 ("wu", C.c_void_p), ("wv", C.c_void_p), ("u0", C.c_float), ("u1", C.c_float), ("v0", C.c_float), ("v1", C.c_float),
                 ("pixW", C.c_int32), ("pixH", C.c_int32), ("Cout", C.c_int32),
                 ("xres", C.c_void_p), ("gamma", C.c_void_p), ("x16_out", C.c_void_p), ("ln_part_out", C.c_void_p),
-                ("q_out", C.c_void_p), ("k_out", C.c_void_p), ("v_out", C.c_void_p), ("nh", C.c_int32), ("Ntok", C.c_int32), ("qscale", C.c_float)]
+                ("q_out", C.c_void_p), ("k_out", C.c_void_p), ("v_out", C.c_void_p), ("nh", C.c_int32), ("Ntok", C.c_int32), ("qscale", C.c_float),
+                ("pos", C.c_void_p), ("cls", C.c_void_p), ("Np", C.c_int32), ("v_transposed", C.c_int32), ("uv_in", C.c_int32)]
 
 
 class TestConvArgs(C.Structure):
@@ -137,10 +138,13 @@ def _load(path: str = LIB_PATH, mode: int = C.RTLD_GLOBAL) -> C.CDLL:
         "moge_test_convt2x2": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, vp]),
         "moge_test_ct3": (C.c_int, [C.POINTER(TestCt3Args), vp]),
         "moge_test_preprocess": (C.c_int, [f32p, f32p, i32, i32, i32, i32, i32, vp]),
+        "moge_test_preprocess_ex": (C.c_int, [i32, i32, f32p, f32p, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "moge_test_resize_bicubic_aa": (C.c_int, [f32p, f32p, i32, i32, i32, i32, i32, vp]),
+        "moge_test_resize_bicubic_aa_ex": (C.c_int, [i32, f32p, f32p, i32, i32, i32, i32, i32, i32, vp]),
         "moge_test_groupnorm_relu": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, vp]),
         "moge_test_norm_act": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),
         "moge_test_posembed": (C.c_int, [f32p, f32p, i32, i32, i32, vp]),
+        "moge_test_posembed_ex": (C.c_int, [f32p, f32p, i32, i32, i32, i32, vp]),
         "moge_test_recover": (C.c_int, [f32p, vp, f32p, i32, i32, i32, f32p, f32p, vp, vp]),
         "moge_test_head_final": (C.c_int, [C.POINTER(TestHeadArgs), vp]),
         "moge_test_head_final_dot": (C.c_int, [i32, i32, f32p, f32p, i32, i32, f32p, f32p, i32, i32, i32, i32, i32, vp]),
@@ -202,6 +206,7 @@ EXPORTS = ["moge_abi_version", "moge_last_error", "moge_create", "moge_create_v1
            "moge_test_resize_bicubic_aa", "moge_test_groupnorm_relu", "moge_test_norm_act", "moge_test_posembed", "moge_test_recover",
            "moge_test_head_final", "moge_test_head_final_dot", "moge_test_mlp_layer", "moge_test_layernorm_ex", "moge_test_ln_raw", "moge_test_ln_finalize",
            "moge_test_fold_ln", "moge_test_resize_bilinear_uv", "moge_test_u8_ingest",
+           "moge_test_preprocess_ex", "moge_test_posembed_ex", "moge_test_resize_bicubic_aa_ex",
            "moge_align_l1", "moge_align_l1_anchored", "moge_align_trunc_workspace", "moge_align_trunc", "moge_align_trunc_anchored",
            "moge_align_select", "moge_align_lstsq",
            "moge_metrics_lr_sample", "moge_metrics_error", "moge_metrics_masked_max", "moge_metrics_boundary", "moge_metrics_segment_stats",

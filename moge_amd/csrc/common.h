@@ -167,9 +167,9 @@ __device__ __forceinline__ void ln_quad_sums(const f32x4& x, float& s1, float& s
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
-// torch.linspace(start, end, steps) element i in fp32 (ATen: symmetric evaluation around the middle)
+// torch.linspace(start, end, steps) element i in fp32 (ATen: symmetric evaluation around the middle; a single step is `start`)
 __device__ __forceinline__ float linspace_at(float start, float end, float step, int steps, int i) {
-    return (i < steps / 2) ? (start + step * (float)i) : (end - step * (float)(steps - 1 - i));
+    return (i < steps / 2 || steps == 1) ? (start + step * (float)i) : (end - step * (float)(steps - 1 - i));
 }
 
 // --------------------------------------------------------------------------------------------

@@ -81,14 +81,30 @@ static int t_gemm_ex(const moge_test_gemm_args& a, hipStream_t st) {
         const int D = a.nh * 64;
         if (N != 3 * D || M % a.Ntok) return MOGE_ERR_INVALID;
         const size_t n = (size_t)M * D;
-        TCHK(qb.alloc(n * sizeof(T))); TCHK(kb.alloc(n * sizeof(T))); TCHK(vb.alloc(n * sizeof(T)));
-        g.epi = EPI_QKV; g.q = qb.p; g.k = kb.p; g.vT = vb.p; g.v_rowmajor = 1;
-        g.nh = a.nh; g.D = D; g.Ntok = a.Ntok; g.Npad = (a.Ntok + 63) / 64 * 64; g.qscale = a.qscale;
+        const int Npad = (a.Ntok + 63) / 64 * 64;
+        // v_transposed: V^T (B,nh,64,Npad) of the fp32 parity path; v_out is IN / OUT there (the key padding [Ntok, Npad) is not the epilogue's to write)
+        const size_t nv = a.v_transposed ? (size_t)(M / a.Ntok) * D * Npad : n;
+        TCHK(qb.alloc(n * sizeof(T))); TCHK(kb.alloc(n * sizeof(T))); TCHK(vb.alloc(nv * sizeof(T)));
+        if (a.v_transposed) TL(to_t<T>(a.v_out, vb.p, (long)nv, st));
+        g.epi = EPI_QKV; g.q = qb.p; g.k = kb.p; g.vT = vb.p; g.v_rowmajor = a.v_transposed ? 0 : 1;
+        g.nh = a.nh; g.D = D; g.Ntok = a.Ntok; g.Npad = Npad; g.qscale = a.qscale;
         break;
     }
     case MOGE_TG_CONVT:
+        if (a.Cout < 4 || (a.Cout & 3) || N != 4 * a.Cout || a.pixW < 1 || a.pixH < 1 || M % (a.pixW * a.pixH)) return MOGE_ERR_INVALID;
         TCHK(ob.alloc(mn * sizeof(T)));
         g.epi = EPI_CONVT; g.out = ob.p; g.Cout = a.Cout;
+        if (a.wu) {          // uv_in: at the INPUT pixel, wu / wv (N) by GEMM column (MoGe-1); else at the output pixel (2 pixH, 2 pixW), wu / wv (Cout)
+            const int sw = a.uv_in ? a.pixW : 2 * a.pixW, sh = a.uv_in ? a.pixH : 2 * a.pixH;
+            g.uv.wu = a.wu; g.uv.wv = a.wv; g.uv.u0 = a.u0; g.uv.u1 = a.u1; g.uv.v0 = a.v0; g.uv.v1 = a.v1;
+            g.uv.ustep = sw > 1 ? (a.u1 - a.u0) / (float)(sw - 1) : 0.f;
+            g.uv.vstep = sh > 1 ? (a.v1 - a.v0) / (float)(sh - 1) : 0.f;
+            g.uv_in = a.uv_in ? 1 : 0;
+        }
+        break;
+    case MOGE_TG_PATCH:
+        if (!a.pos || !a.xres || a.Np < 1 || M % a.Np || a.Ntok < 1 + a.Np) return MOGE_ERR_INVALID;
+        g.epi = EPI_PATCH; g.xres = a.xres; g.pos = a.pos; g.cls = a.cls; g.Np = a.Np; g.Ntok = a.Ntok;
         break;
     default: return MOGE_ERR_INVALID;
     }
@@ -97,7 +113,8 @@ static int t_gemm_ex(const moge_test_gemm_args& a, hipStream_t st) {
     if (a.kind == MOGE_TG_RESID && a.x16_out) TL((launch_convert<f16, float>(x16.p, a.x16_out, (long)mn, st)));
     if (a.kind == MOGE_TG_QKV) {
         const long n = (long)M * a.nh * 64;
-        TL(from_t<T>(qb.p, a.q_out, n, st)); TL(from_t<T>(kb.p, a.k_out, n, st)); TL(from_t<T>(vb.p, a.v_out, n, st));
+        const long nv = a.v_transposed ? (long)(M / a.Ntok) * a.nh * 64 * g.Npad : n;
+        TL(from_t<T>(qb.p, a.q_out, n, st)); TL(from_t<T>(kb.p, a.k_out, n, st)); TL(from_t<T>(vb.p, a.v_out, nv, st));
     }
     TCHK(hipStreamSynchronize(st));
     return 0;
@@ -390,7 +407,71 @@ static int t_u8_ingest(const uint8_t* in, float* out, int B, int H, int W, hipSt
     return 0;
 }
 
+// preprocess_kernel through launch_preprocess with every argument the model passes.  `out` is IN / OUT (the caller's pre-fill, converted to the storage
+// type and back), n elements; zero_i32 is the caller's own device buffer.
+template <typename TIn, typename TOut>
+static int t_preprocess_ex(const float* image, float* out, int32_t* zero_i32, int B, int H, int W, int rows, int cols, int ldk, int nchw_out, int round16,
+                           int aa, int zero_n, hipStream_t st) {
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f};
+    const long nin = (long)B * 3 * H * W;
+    const long nout = nchw_out ? (long)B * 3 * rows * 14 * cols * 14 : (long)B * rows * cols * ldk;
+    DevBuf ib, ob;
+    const void* ip = image;
+    void* op = out;
+    if (std::is_same<TIn, f16>::value) {
+        TCHK(ib.alloc((size_t)nin * sizeof(f16)));
+        TL((launch_convert<float, f16>(image, ib.p, nin, st)));
+        ip = ib.p;
+    }
+    if (std::is_same<TOut, f16>::value) {
+        TCHK(ob.alloc((size_t)nout * sizeof(f16)));
+        TL((launch_convert<float, f16>(out, ob.p, nout, st)));
+        op = ob.p;
+    }
+    TL((launch_preprocess<TIn, TOut>(ip, op, B, H, W, rows, cols, ldk, nchw_out, round16, aa, mean, sd, st, zero_i32, zero_n)));
+    if (std::is_same<TOut, f16>::value) TL((launch_convert<f16, float>(ob.p, out, nout, st)));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" {
+
+int moge_test_preprocess_ex(int in_fp16, int out_fp16, const float* image, float* out, int32_t* zero_i32, int B, int H, int W, int rows, int cols, int ldk,
+                            int nchw_out, int round16, int aa, int zero_n, void* stream) {
+    if (!image || !out || B < 1 || H < 1 || W < 1 || rows < 1 || cols < 1 || zero_n < 0 || (zero_n && !zero_i32)) return MOGE_ERR_INVALID;
+    if (!nchw_out && ldk < 1) return MOGE_ERR_INVALID;                   // (what the launcher accepts of ldk is the launcher's to say)
+    if (in_fp16 && round16) return MOGE_ERR_INVALID;                     // round16 is the fp32 image of a .half() model
+    hipStream_t st = (hipStream_t)stream;
+    if (in_fp16) return out_fp16 ? t_preprocess_ex<f16, f16>(image, out, zero_i32, B, H, W, rows, cols, ldk, nchw_out, round16, aa, zero_n, st)
+                                 : t_preprocess_ex<f16, float>(image, out, zero_i32, B, H, W, rows, cols, ldk, nchw_out, round16, aa, zero_n, st);
+    return out_fp16 ? t_preprocess_ex<float, f16>(image, out, zero_i32, B, H, W, rows, cols, ldk, nchw_out, round16, aa, zero_n, st)
+                    : t_preprocess_ex<float, float>(image, out, zero_i32, B, H, W, rows, cols, ldk, nchw_out, round16, aa, zero_n, st);
+}
+
+int moge_test_posembed_ex(const float* pos, float* out, int D, int rows, int cols, int size_mode, void* stream) {
+    if (!pos || !out || D < 1 || rows < 1 || cols < 1) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    TL(launch_posembed(pos, out, D, rows, cols, size_mode ? 1 : 0, st));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int moge_test_resize_bicubic_aa_ex(int in_fp16, const float* image, float* out, int B, int H, int W, int OH, int OW, int round16, void* stream) {
+    if (!image || !out || B < 1 || H < 1 || W < 1 || OH < 1 || OW < 1) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (in_fp16) {
+        const long nin = (long)B * 3 * H * W;
+        DevBuf ib;
+        TCHK(ib.alloc((size_t)nin * sizeof(f16)));
+        TL((launch_convert<float, f16>(image, ib.p, nin, st)));
+        TL(launch_resize_bicubic_aa<f16>(ib.p, out, B, H, W, OH, OW, round16 ? 1 : 0, st));
+        TCHK(hipStreamSynchronize(st));
+        return 0;
+    }
+    TL(launch_resize_bicubic_aa<float>(image, out, B, H, W, OH, OW, round16 ? 1 : 0, st));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
 
 int moge_test_head_final(const moge_test_head_args* a, void* stream) {
     if (!a || !a->x || !a->w || !a->bias || !a->out || (a->n4 && !a->w2)) return MOGE_ERR_INVALID;

@@ -40,12 +40,15 @@ def gemm(prec, A, W, bias=None, act=0):
     return C
 
 
-TG_STORE, TG_RESID, TG_QKV, TG_CONVT = 0, 1, 2, 3
+TG_STORE, TG_RESID, TG_QKV, TG_CONVT, TG_PATCH = 0, 1, 2, 3, 4
 
 
 def gemm_ex(kind, A, W, bias, prec=1, act=0, ln_mr=None, ln_c=None, uv=None, pix=None, Cout=0, xres=None, gamma=None, want_x16=False,
-            nh=0, Ntok=0, qscale=1.0, x16_stream=None, want_part=True):
-    """One GEMM through a fused epilogue (moge_test_gemm_ex).  All tensors fp32 on the GPU.  Returns a dict of outputs."""
+            nh=0, Ntok=0, qscale=1.0, x16_stream=None, want_part=True, pos=None, cls=None, Np=0, v_prefill=None, uv_in=False, raw=False):
+    """One GEMM through a fused epilogue (moge_test_gemm_ex).  All tensors fp32 on the GPU.  Returns a dict of outputs.
+    TG_PATCH: xres (B Ntok, N) is the pre-filled residual stream, pos (1 + Np, N), cls (N) or None.  TG_QKV with v_prefill (B, nh, 64, Npad): the
+    transposed V of the fp32 path, returned whole.  TG_CONVT with uv and uv_in: the uv term at the input pixel, wu / wv by GEMM column.
+    raw=True returns the status code instead of raising."""
     import ctypes as C
     A, W = _f(A), _f(W)
     M, K = A.shape
@@ -71,7 +74,10 @@ def gemm_ex(kind, A, W, bias, prec=1, act=0, ln_mr=None, ln_c=None, uv=None, pix
     out = {}
     if kind in (TG_STORE, TG_CONVT):
         out["out"] = torch.empty((M, N), device="cuda", dtype=torch.float32)
-        a.out, a.Cout = out["out"].data_ptr(), Cout
+        a.out, a.Cout, a.uv_in = out["out"].data_ptr(), Cout, int(bool(uv_in))
+    elif kind == TG_PATCH:
+        out["xres"] = _f(xres).clone()
+        a.xres, a.pos, a.cls, a.Np, a.Ntok = out["xres"].data_ptr(), dev(pos), dev(cls), Np, Ntok
     elif kind == TG_RESID and x16_stream is not None:
         # fp16 residual stream of a `.half()` model (EPK_RESID16): x16 in / out (fp32 values that are exact fp16 numbers), xres = NULL
         out["x16"] = _f(x16_stream).clone()
@@ -90,9 +96,15 @@ def gemm_ex(kind, A, W, bias, prec=1, act=0, ln_mr=None, ln_c=None, uv=None, pix
         B = M // Ntok
         for k in ("q", "k", "v"):
             out[k] = torch.empty((B, nh, Ntok, 64), device="cuda", dtype=torch.float32)
+        if v_prefill is not None:
+            assert tuple(v_prefill.shape) == (B, nh, 64, (Ntok + 63) // 64 * 64)
+            out["v"], a.v_transposed = _f(v_prefill).clone(), 1
         a.q_out, a.k_out, a.v_out = out["q"].data_ptr(), out["k"].data_ptr(), out["v"].data_ptr()
         a.nh, a.Ntok, a.qscale = nh, Ntok, qscale
-    L.check(L.lib.moge_test_gemm_ex(C.byref(a), st()))
+    rc = L.lib.moge_test_gemm_ex(C.byref(a), st())
+    if raw:
+        return rc
+    L.check(rc)
     return out
 
 
@@ -143,6 +155,40 @@ def posembed(pos, rows, cols):
     D = pos.shape[-1]
     y = torch.empty((1 + rows * cols, D), device="cuda", dtype=torch.float32)
     L.check(L.lib.moge_test_posembed(_p(pos), _p(y), D, rows, cols, st()))
+    return y
+
+
+def posembed_ex(pos, rows, cols, size_mode):
+    pos = _f(pos)
+    D = pos.shape[-1]
+    y = torch.full((1 + rows * cols, D), float("nan"), device="cuda", dtype=torch.float32)
+    L.check(L.lib.moge_test_posembed_ex(_p(pos), _p(y), D, rows, cols, int(bool(size_mode)), st()))
+    return y
+
+
+def preprocess_ex(img, rows, cols, out_prefill, in_fp16=False, out_fp16=False, ldk=640, nchw_out=False, round16=False, aa=True, counters=None, zero_n=0,
+                  raw=False):
+    """preprocess_kernel as the model launches it (moge_test_preprocess_ex).  out_prefill: (B rows cols, ldk), or (B,3,14 rows,14 cols) with nchw_out;
+    counters: int32 tensor (zero_n entries + a guard) or None.  Both are copied, handed to the kernel and returned whole."""
+    img = _f(img)
+    B, _, H, W = img.shape
+    y = _f(out_prefill).clone()
+    assert y.numel() == (B * 3 * rows * 14 * cols * 14 if nchw_out else B * rows * cols * max(ldk, 0))
+    cnt = None if counters is None else counters.detach().to("cuda", torch.int32).contiguous().clone()
+    assert cnt is None or cnt.numel() >= zero_n
+    rc = L.lib.moge_test_preprocess_ex(int(bool(in_fp16)), int(bool(out_fp16)), _p(img), _p(y), _p(cnt), B, H, W, rows, cols, ldk, int(bool(nchw_out)),
+                                       int(bool(round16)), int(bool(aa)), zero_n, st())
+    if raw:
+        return rc
+    L.check(rc)
+    return y, cnt
+
+
+def resize_bicubic_aa_ex(img, OH, OW, in_fp16=False, round16=False):
+    img = _f(img)
+    B, _, H, W = img.shape
+    y = torch.full((B, 3, OH, OW), float("nan"), device="cuda", dtype=torch.float32)
+    L.check(L.lib.moge_test_resize_bicubic_aa_ex(int(bool(in_fp16)), _p(img), _p(y), B, H, W, OH, OW, int(bool(round16)), st()))
     return y
 
 
