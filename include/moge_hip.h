@@ -497,6 +497,42 @@ int moge_refine_depth_workspace(int B, int H, int W, int64_t* bytes);
 int moge_refine_depth(const float* depth, const float* normal, const float* intrinsics, const uint8_t* mask, int B, int H, int W, int kernel_size,
                       int iterations, float damp, float eps, void* workspace, float* out, void* stream);
 
+/* ---- image mesh and masked point cloud (moge_amd/io.py build_mesh_from_map, masked_point_cloud: the host functions are the specification;
+ * python mirror moge_amd/mesh.py) --------------------------------------------------------------------------------
+ * Stateless (no handle); every pointer is device memory unless stated; results are written asynchronously on `stream`.  Stream compaction
+ * over the H * W pixels of each of B images, in two phases because the output sizes depend on the data:
+ *   count   mask (B, H, W) u8 (non-zero = true) or NULL (all true).  points = 0: a quad (i, j) is valid when i < H-1, j < W-1 and the mask holds at
+ *           its four pixels; a pixel is used when one of the up to four quads touching it is valid.  points = 1: a pixel is used when the mask
+ *           holds, and there are no quads.  -> counts (B, 2) int32 = (vertices, quads) per image, offsets (B, 2) int64 = the exclusive sums of
+ *           counts over the images: where image b starts in outputs that hold the images one after the other.
+ *   fill    the same B, H, W and workspace, after count on the same stream.  Used pixels are numbered row-major; map k's row (offsets[b][0] + new
+ *           index) of out (total vertices, channels) fp32 takes the pixel's values: MOGE_MESH_F32 data (B, H, W, channels) fp32, bits unchanged
+ *           (NaN, inf, -0.0); MOGE_MESH_U8 data u8, x / 255; MOGE_MESH_UV no data (NULL), channels = 2, ((j + 0.5) / W, (i + 0.5) / H) - both in
+ *           correctly rounded fp32 divisions.  has_scale / has_offset: then x * scale[c] and + offset[c], a separate fp32 multiply and add.
+ *           Faces, with the Q valid quads of image b ranked row-major, q0 = offsets[b][1] and a, b, c, d the new indices (inside image b) of
+ *           (i, j), (i+1, j), (i+1, j+1), (i, j+1): tri = 1: faces (2 * total quads, 3) int32, rows 2 q0 + r = (a, b, c) and 2 q0 + Q + r =
+ *           (a, c, d); tri = 0: faces (total quads, 4), row q0 + r = (a, b, c, d); tri = MOGE_MESH_NO_FACES: none (faces may be NULL).
+ *           `maps` is a HOST array read during the call; offsets may be any non-overlapping layout, not only the one count wrote.
+ * Limits: 0 <= B <= 65535, H, W >= 1 (H = 1 or W = 1: no quads), H * W < 2^31, at most MOGE_MESH_MAX_MAPS maps of 1 ... 4 channels: otherwise
+ * MOGE_ERR_INVALID, as for a NULL required pointer, before anything is launched.  workspace: moge_image_mesh_workspace(B, H, W) bytes =
+ * B * (8 * (nblk + nspan + 1) + 5 * H * W) with nblk = ceil(H * W / MOGE_MESH_BLOCK_PX) and nspan = ceil(nblk / MOGE_MESH_SCAN_SPAN) (pure
+ * arithmetic, no GPU needed), 8-byte aligned.  No atomics: two calls give the same bits, and an image gives the same bits alone as inside a batch. */
+#define MOGE_MESH_MAX_MAPS 8
+#define MOGE_MESH_BLOCK_PX 1024            /* consecutive pixels one workgroup of the scan ranks */
+#define MOGE_MESH_SCAN_SPAN 256            /* workgroup totals one workgroup of the second scan level covers */
+#define MOGE_MESH_NO_FACES (-1)
+typedef enum moge_mesh_dtype { MOGE_MESH_F32 = 0, MOGE_MESH_U8 = 1, MOGE_MESH_UV = 2 } moge_mesh_dtype;
+typedef struct moge_mesh_map {
+    const void* data;                      /* (B, H, W, channels), contiguous; NULL for MOGE_MESH_UV */
+    float* out;                            /* (total vertices, channels) */
+    int32_t channels, dtype, has_scale, has_offset;
+    float scale[4], offset[4];
+} moge_mesh_map;
+int moge_image_mesh_workspace(int B, int H, int W, int64_t* bytes);
+int moge_image_mesh_count(const uint8_t* mask, int B, int H, int W, int points, void* workspace, int32_t* counts, int64_t* offsets, void* stream);
+int moge_image_mesh_fill(int B, int H, int W, void* workspace, const moge_mesh_map* maps, int n_maps, int tri, int32_t* faces, const int64_t* offsets,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

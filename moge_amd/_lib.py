@@ -23,6 +23,8 @@ ACTIVATION = {"relu": 0, "leaky_relu": 1, "silu": 2, "elu": 3}                  
 ERR_NONFINITE = -5
 KC_NAMES = ["gemm", "attn", "conv", "norm", "pre", "post", "recover", "gemm_pp"]
 ABI_VERSION = 5
+MESH_MAX_MAPS, MESH_BLOCK_PX, MESH_SCAN_SPAN, MESH_NO_FACES = 8, 1024, 256, -1       # include/moge_hip.h MOGE_MESH_*
+MESH_F32, MESH_U8, MESH_UV = 0, 1, 2                                                  # moge_mesh_dtype
 
 
 class MogeConfig(C.Structure):
@@ -91,6 +93,12 @@ class TestHeadArgs(C.Structure):
     _fields_ = [("precision", C.c_int32), ("kind", C.c_int32), ("remap", C.c_int32), ("ksize", C.c_int32),
                 ("B", C.c_int32), ("Hd", C.c_int32), ("Wd", C.c_int32), ("C", C.c_int32), ("ld", C.c_int32), ("choff", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("n4_below", C.c_int32), ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("n4", C.c_void_p), ("w2", C.c_void_p), ("out", C.c_void_p)]
+
+
+class MeshMap(C.Structure):
+    """moge_mesh_map: one attribute map of moge_image_mesh_fill (dtype MESH_F32 / MESH_U8 / MESH_UV)."""
+    _fields_ = [("data", C.c_void_p), ("out", C.c_void_p), ("channels", C.c_int32), ("dtype", C.c_int32), ("has_scale", C.c_int32),
+                ("has_offset", C.c_int32), ("scale", C.c_float * 4), ("offset", C.c_float * 4)]
 
 
 class MogeError(RuntimeError):
@@ -178,6 +186,9 @@ def _load(path: str = LIB_PATH, mode: int = C.RTLD_GLOBAL) -> C.CDLL:
         "moge_eval_unproject": (C.c_int, [vp, vp, i32, i32, f32p, vp, vp, vp]),
         "moge_refine_depth_workspace": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
         "moge_refine_depth": (C.c_int, [f32p, f32p, f32p, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, f32p, vp]),
+        "moge_image_mesh_workspace": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
+        "moge_image_mesh_count": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "moge_image_mesh_fill": (C.c_int, [i32, i32, i32, vp, C.POINTER(MeshMap), i32, i32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so does not export what the header declares
@@ -213,7 +224,8 @@ EXPORTS = ["moge_abi_version", "moge_last_error", "moge_create", "moge_create_v1
            "moge_metrics_segment_pack", "moge_metrics_segment_error",
            "moge_eval_lanczos_workspace", "moge_eval_lanczos", "moge_eval_masked_nearest", "moge_eval_resize_nearest", "moge_eval_remap",
            "moge_eval_quantile_cut", "moge_eval_unproject",
-           "moge_refine_depth_workspace", "moge_refine_depth"]
+           "moge_refine_depth_workspace", "moge_refine_depth",
+           "moge_image_mesh_workspace", "moge_image_mesh_count", "moge_image_mesh_fill"]
 
 
 def check(code: int) -> None:

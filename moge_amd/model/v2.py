@@ -527,6 +527,20 @@ class MoGeModel:
             res["points"] = torch.where(scaled[..., None], output["points"] * (refined / depth)[..., None], output["points"])
         return res
 
+    @torch.inference_mode()
+    def image_mesh(self, output: Dict[str, torch.Tensor], image_u8: torch.Tensor, rtol: float = 0.04, tri: bool = True):
+        """The export mesh of an `infer()` output (batched or not) on the device: the mask cleaned by `depth_edge_mask(depth, mask, rtol)`, then
+        `moge_amd.mesh.export_mesh` over it.  image_u8: the uint8 (H, W, 3) / (B, H, W, 3) image the output came from (any device).
+        -> faces, vertices, vertex_colors, vertex_uvs[, vertex_normals] in the export convention (a list of such tuples for a batch): what
+        scripts/infer.py hands to save_glb / save_ply.  One host read-back (the counts).  ValueError if the output has no `points` / `depth`."""
+        from ..mesh import export_mesh
+        if "points" not in output or "depth" not in output:
+            raise ValueError("image_mesh needs 'points' and 'depth' in the output (the points head)")
+        clean = self.depth_edge_mask(output["depth"], output.get("mask"), rtol=rtol)
+        normal = output.get("normal")
+        return export_mesh(output["points"].to(self._device, torch.float32), image_u8.to(self._device), clean,
+                           None if normal is None else normal.to(self._device, torch.float32), tri=tri)
+
     def _infer_device(self, image, img_dtype, B, H, W, omit_batch_dim, num_tokens, resolution_level, force_projection, apply_mask, fov_x, use_fp16):
         if num_tokens is None:
             min_tokens, max_tokens = self.num_tokens_range

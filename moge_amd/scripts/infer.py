@@ -6,7 +6,9 @@ images of equal size are batched (`--batch`) and run through
 `moge_amd.pipeline.InferPipeline` (uint8 upload, transfers overlapped with compute).  Differences, all forced by what this image ships:
 decode / resize use PIL instead of cv2 (BOX filter for `--resize`, the closest PIL has to INTER_AREA); `depth.exr` / `points.exr` are
 written by moge_amd.io.save_exr (uncompressed float32 OpenEXR, same channels as cv2 writes); `mesh.glb` by moge_amd.io.save_glb (glTF 2.0
-binary written directly - trimesh is not installed; same material parameters as moge/utils/io.py:18-42).  Mesh and point cloud are built from `mask & ~depth_map_edge(depth, rtol=threshold)` exactly as scripts/infer.py:127-149 does.
+binary written directly - trimesh is not installed; same material parameters as moge/utils/io.py:18-42).  Mesh and point cloud are built from `mask & ~depth_map_edge(depth, rtol=threshold)` exactly as scripts/infer.py:127-149 does,
+on the GPU by `moge_amd.mesh.export_mesh` (the batch's points, image and normal are uploaded, the compacted arrays come back); `--host_mesh` keeps
+the numpy path of `moge_amd.io.build_mesh_from_map`, and both write the same bytes.
 """
 from __future__ import annotations
 
@@ -37,12 +39,14 @@ import numpy as np
 @click.option("--ply", "save_ply_", is_flag=True, help="Save a coloured point cloud (.ply).")
 @click.option("--show", "show", is_flag=True, help="Accepted for compatibility: the reference opens a trimesh viewer here, which this image does not ship.")
 @click.option("--batch", "batch", type=int, default=8, help="Images of equal size per infer() call.")
+@click.option("--host_mesh", "host_mesh", is_flag=True, help="Build the mesh on the host (numpy) instead of the GPU; the files are the same.")
 def main(input_path, fov_x_, output_path, pretrained_model_name_or_path, model_version, device_name, use_fp16, resize_to, resolution_level, num_tokens,
-         threshold, save_maps_, save_glb_, save_ply_, show, batch):
+         threshold, save_maps_, save_glb_, save_ply_, show, batch, host_mesh=False):
     import torch
     from PIL import Image
 
     from moge_amd.io import build_mesh_from_map, colorize_depth, colorize_normal, save_exr, save_glb, save_ply, uv_map
+    from moge_amd.mesh import export_mesh
     from moge_amd.model import import_model_class_by_version
     from moge_amd.pipeline import InferPipeline
 
@@ -95,10 +99,16 @@ def main(input_path, fov_x_, output_path, pretrained_model_name_or_path, model_v
 
         for ch, out in zip(chunks, pipe.run(gen())):
             imgs = loaded.pop(0)
-            cleaned = None
+            cleaned = meshes = None
             if save_ply_ or save_glb_:
-                cleaned = model.depth_edge_mask(torch.from_numpy(out["depth"]), torch.from_numpy(out["mask"]) if "mask" in out else None,
-                                                rtol=threshold).cpu().numpy()
+                cleaned = model.depth_edge_mask(torch.from_numpy(out["depth"]), torch.from_numpy(out["mask"]) if "mask" in out else None, rtol=threshold)
+                if host_mesh:
+                    cleaned = cleaned.cpu().numpy()
+                else:                                   # the whole batch in one call, already in the export convention; only the compacted arrays come back
+                    dev = cleaned.device
+                    meshes = export_mesh(torch.from_numpy(out["points"]).to(dev), torch.from_numpy(imgs).to(dev), cleaned,
+                                         torch.from_numpy(out["normal"]).to(dev) if "normal" in out else None, tri=True)
+                    meshes = [[t.cpu().numpy() for t in m] for m in meshes]
             for j, p in enumerate(ch):
                 save_path = Path(output_path, p.relative_to(root).parent, p.stem)
                 save_path.mkdir(exist_ok=True, parents=True)
@@ -115,16 +125,19 @@ def main(input_path, fov_x_, output_path, pretrained_model_name_or_path, model_v
                     with open(save_path / "fov.json", "w") as f:           # normalised intrinsics: fov = 2 atan(0.5 / f)
                         json.dump({"fov_x": round(math.degrees(2 * math.atan(0.5 / float(K[0, 0]))), 2),
                                    "fov_y": round(math.degrees(2 * math.atan(0.5 / float(K[1, 1]))), 2)}, f)
-                if save_glb_ or save_ply_:
+                if meshes is not None:
+                    faces, vertices, vertex_colors, vertex_uvs, *rest = meshes[j]
+                    vertex_normals = rest[0] if rest else None
+                elif save_glb_ or save_ply_:
                     maps = [out["points"][j], imgs[j].astype(np.float32) / 255, uv_map(h, w)] + ([out["normal"][j]] if "normal" in out else [])
                     faces, vertices, vertex_colors, vertex_uvs, *rest = build_mesh_from_map(*maps, mask=cleaned[j], tri=True)
                     # OpenGL conventions for the export (scripts/infer.py:146-151): x right, y up, z backward; (0, 0) = left-bottom of the texture
                     vertices, vertex_uvs = vertices * [1, -1, -1], vertex_uvs * [1, -1] + [0, 1]
                     vertex_normals = rest[0] * [1, -1, -1] if rest else None
-                    if save_glb_:
-                        save_glb(save_path / "mesh.glb", vertices, faces, vertex_uvs, imgs[j], vertex_normals)
-                    if save_ply_:
-                        save_ply(save_path / "pointcloud.ply", vertices, np.zeros((0, 3), dtype=np.int32), vertex_colors, vertex_normals)
+                if save_glb_:
+                    save_glb(save_path / "mesh.glb", vertices, faces, vertex_uvs, imgs[j], vertex_normals)
+                if save_ply_:
+                    save_ply(save_path / "pointcloud.ply", vertices, np.zeros((0, 3), dtype=np.int32), vertex_colors, vertex_normals)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,10 @@ the mesh mask is `mask & ~depth_map_edge(z, rtol=threshold)` where the reference
 un-vendored: not restated) - a superset of the reference's removed pixels.  One reference quirk is NOT mirrored: its mesh export reads the
 `depth` variable left over from the `--maps` loop (:123), so `--ply` without `--maps` raises NameError there; here the depth of the mesh mask is
 the point map's z.  `depth_affine_invariant` / `disparity_affine_invariant` get the plain depth colour map (their affine-aware colourings live in
-moge/utils/vis.py, which no MoGe plugin output reaches)."""
+moge/utils/vis.py, which no MoGe plugin output reaches).  The mesh is built on the plugin's device by `moge_amd.mesh` (points, image and mask are
+uploaded, the compacted arrays come back); `--host_mesh` (read from the arguments left for the plugin, so that the declared options stay the
+reference's) keeps the numpy path of `moge_amd.io.build_mesh_from_map`, and both write the same bytes; a plugin whose `device` is not a GPU gets
+the numpy path without being asked."""
 from __future__ import annotations
 
 import importlib.util
@@ -35,7 +38,8 @@ def import_file_as_module(file_path, module_name: str):
     return module
 
 
-@click.command(context_settings={"allow_extra_args": True, "ignore_unknown_options": True}, help="Inference script for wrapped baseline methods (MI355X)")
+@click.command(context_settings={"allow_extra_args": True, "ignore_unknown_options": True},
+               help="Inference script for wrapped baseline methods (MI355X).  --host_mesh: build the mesh on the host (numpy) instead of the GPU; the files are the same.")
 @click.option("--baseline", "baseline_code_path", required=True, type=click.Path(), help="Path to the baseline model python code.")
 @click.option("--input", "-i", "input_path", type=str, required=True, help="Input image or folder")
 @click.option("--output", "-o", "output_path", type=str, default="./output", help="Output folder")
@@ -51,9 +55,13 @@ def main(ctx, baseline_code_path, input_path, output_path, image_size, skip, sav
     from PIL import Image
 
     from moge_amd.io import build_mesh_from_map, colorize_depth, depth_map_edge, save_exr, save_glb, save_ply, uv_map
+    from moge_amd.mesh import export_mesh
 
+    # `--host_mesh` is this script's flag and not one of the reference command's options (the set above is the reference's, infer_baseline.py:17-26):
+    # it is taken out of the arguments that go on to the plugin
+    host_mesh = "--host_mesh" in ctx.args
     module = import_file_as_module(baseline_code_path, Path(baseline_code_path).stem)
-    baseline = getattr(module, "Baseline").load.main(ctx.args, standalone_mode=False)
+    baseline = getattr(module, "Baseline").load.main([a for a in ctx.args if a != "--host_mesh"], standalone_mode=False)
 
     suffices = ["jpg", "png", "jpeg", "JPG", "PNG", "JPEG"]
     if Path(input_path).is_dir():
@@ -108,13 +116,19 @@ def main(ctx, baseline_code_path, input_path, output_path, image_size, skip, sav
             on_device = getattr(getattr(baseline, "model", None), "depth_edge_mask", None)          # a moge_amd model behind the plugin: the device kernel
             if on_device is not None:
                 z = np.where(mask, points[..., 2], np.nan).astype(np.float32)
-                clean = on_device(torch.from_numpy(z), torch.from_numpy(mask), rtol=threshold).cpu().numpy()
+                clean = on_device(torch.from_numpy(z), torch.from_numpy(mask), rtol=threshold)
             else:
-                clean = mask & ~depth_map_edge(points[..., 2].astype(np.float32), threshold, mask=mask)
-            faces, vertices, vertex_colors, vertex_uvs = build_mesh_from_map(np.where(mask[..., None], points, 0).astype(np.float32), image_np.astype(np.float32) / 255,
-                                                                             uv_map(height, width), mask=clean, tri=True)
-            # OpenGL conventions for the export (infer_baseline.py:127-130): x right, y up, z backward; (0, 0) = left-bottom of the texture
-            vertices, vertex_uvs = vertices * [1, -1, -1], vertex_uvs * [1, -1] + [0, 1]
+                clean = torch.from_numpy(mask & ~depth_map_edge(points[..., 2].astype(np.float32), threshold, mask=mask))
+            masked_points = np.where(mask[..., None], points, 0).astype(np.float32)
+            dev = clean.device if clean.is_cuda else torch.device(baseline.device)
+            if host_mesh or dev.type != "cuda":         # a plugin that runs on the CPU has no device to build the mesh on: the numpy path, as before
+                faces, vertices, vertex_colors, vertex_uvs = build_mesh_from_map(masked_points, image_np.astype(np.float32) / 255, uv_map(height, width),
+                                                                                 mask=clean.cpu().numpy(), tri=True)
+                # OpenGL conventions for the export (infer_baseline.py:127-130): x right, y up, z backward; (0, 0) = left-bottom of the texture
+                vertices, vertex_uvs = vertices * [1, -1, -1], vertex_uvs * [1, -1] + [0, 1]
+            else:                                       # the same arrays, already in the export convention, compacted on the plugin's device
+                faces, vertices, vertex_colors, vertex_uvs = (t.cpu().numpy() for t in export_mesh(
+                    torch.from_numpy(masked_points).to(dev), torch.from_numpy(image_np).to(dev), clean.to(dev), tri=True))
             if save_glb_:
                 save_glb(save_path / "mesh.glb", vertices, faces, vertex_uvs, image_np)
             if save_ply_:

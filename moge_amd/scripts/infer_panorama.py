@@ -11,7 +11,9 @@ reference (infer_panorama.py:101).  File conventions: by default the outputs are
 R, G, B = x, y, z; the GLB's uvs in the v-up convention `moge_amd.io.save_glb` expects, so the texture is upright).  The reference's panorama script
 differs from its own `scripts/infer.py` in two places - :132 writes `points` through cv2 without the RGB -> BGR conversion of `infer.py:114` (file channels
 R, G, B = z, y, x) and :147 passes the mesh builder's uvs unflipped (`infer.py:148` flips v) - and whether the second one shows as a mirrored texture depends on
-the un-vendored utils3d / trimesh conventions; `--reference_compat` reproduces both byte conventions for callers that parse the reference's files."""
+the un-vendored utils3d / trimesh conventions; `--reference_compat` reproduces both byte conventions for callers that parse the reference's files.  The mesh is built on the GPU by
+`moge_amd.mesh.build_mesh_from_map` (points, image and the cleaned mask go up, the compacted arrays come back); `--host_mesh` keeps the numpy path of
+`moge_amd.io.build_mesh_from_map`, and both write the same bytes."""
 from __future__ import annotations
 
 import itertools
@@ -40,12 +42,14 @@ import numpy as np
 @click.option("--show", "show", is_flag=True, help="Accepted for compatibility: the reference opens a trimesh viewer here, which this image does not ship.")
 @click.option("--reference_compat", "reference_compat", is_flag=True,
               help="Write points.exr (R, G, B = z, y, x) and the GLB uvs (unflipped) exactly as the reference's panorama script does; default: the conventions of `moge infer`.")
+@click.option("--host_mesh", "host_mesh", is_flag=True, help="Build the mesh on the host (numpy) instead of the GPU; the files are the same.")
 def main(input_path, output_path, pretrained_model_name_or_path, model_version, device_name, use_fp16, resize_to, resolution_level, threshold,
-         batch_size, save_splitted, save_maps_, save_glb_, save_ply_, show, reference_compat=False):
+         batch_size, save_splitted, save_maps_, save_glb_, save_ply_, show, reference_compat=False, host_mesh=False):
     import torch
     from PIL import Image
 
     from moge_amd.io import build_mesh_from_map, colorize_depth, save_exr, save_glb, save_ply, uv_map
+    from moge_amd.mesh import UV, build_mesh_from_map as device_mesh_from_map
     from moge_amd.model import import_model_class_by_version
     from moge_amd.panorama import infer_panorama
 
@@ -95,8 +99,13 @@ def main(input_path, output_path, pretrained_model_name_or_path, model_version, 
             save_exr(save_path / "points.exr", points[..., ::-1] if reference_compat else points)
             Image.fromarray((mask * 255).astype(np.uint8)).save(save_path / "mask.png")
         if save_glb_ or save_ply_:
-            cleaned = model.depth_edge_mask(torch.from_numpy(depth)[None], torch.from_numpy(mask)[None], rtol=threshold).cpu().numpy()[0]
-            faces, vertices, vertex_colors, vertex_uvs = build_mesh_from_map(points, image.astype(np.float32) / 255, uv_map(H, W), mask=cleaned, tri=True)
+            cleaned = model.depth_edge_mask(torch.from_numpy(depth)[None], torch.from_numpy(mask)[None], rtol=threshold)[0]
+            if host_mesh:
+                faces, vertices, vertex_colors, vertex_uvs = build_mesh_from_map(points, image.astype(np.float32) / 255, uv_map(H, W), mask=cleaned.cpu().numpy(), tri=True)
+            else:                                       # this command does not flip the vertices on either path; the uvs are flipped below, on the compacted array
+                dev = cleaned.device
+                faces, vertices, vertex_colors, vertex_uvs = (t.cpu().numpy() for t in device_mesh_from_map(
+                    torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(dev), torch.from_numpy(image).to(dev), UV, mask=cleaned, tri=True))
             if save_glb_:
                 # save_glb takes OpenGL (v-up) uvs and flips them back to glTF's top-left origin: hand it v-up uvs so the texture is upright
                 # (--reference_compat: the builder's v-down uvs as infer_panorama.py:147 passes them)
