@@ -533,6 +533,54 @@ int moge_image_mesh_count(const uint8_t* mask, int B, int H, int W, int points, 
 int moge_image_mesh_fill(int B, int H, int W, void* workspace, const moge_mesh_map* maps, int n_maps, int tri, int32_t* faces, const int64_t* offsets,
                          void* stream);
 
+/* ---- panorama split and merge (moge_amd/panorama.py split_panorama_image, merge_panorama_depth: the host functions are the specification;
+ * python mirror moge_amd/panorama_gpu.py) ---------------------------------------------------------------------------
+ * Stateless (no handle); every pointer is device memory unless stated.  extrinsics (n, 4, 4) and intrinsics (n, 3, 3) are HOST arrays of fp32,
+ * read during the call (world -> camera rotation of a camera at the origin; normalised intrinsics), 1 <= n <= MOGE_PANO_MAX_VIEWS.  A panorama
+ * map is (height, width) with width, height >= 1 (a coarse level of a flat map may be one pixel high; the Python surface asks for 2) and
+ * width * height <= MOGE_PANO_MAX_PIXELS; bad sizes and NULL required pointers come back
+ * MOGE_ERR_INVALID with a message before anything is launched.
+ *
+ * The least-squares system of the merge is never stored.  Its rows, for N = width * height pixels, in this order (M rows in all):
+ *   N                      x[i, j] - x[i, (j+1) % width]
+ *   (height-1) * width     x[i, j] - x[i+1, j]
+ *   height-1               the column-0 rows of the previous block once more (the reference enters them twice)
+ *   N                      x[i-1, j] + x[i+1, j] + x[i, j-1] + x[i, j+1] - 4 x[i, j] (x wraps, the top / bottom row is replicated)
+ * b (M) fp64 and rows (M) u8 hold the right-hand side and which rows take part; the others are zero rows.
+ *
+ * workspace (system and lsmr): moge_pano_merge_workspace bytes = 8 * (M + 3 N + 3 P + MOGE_PANO_STATE_DOUBLES) + 5 * n * N with
+ * P = ceil(M / MOGE_PANO_SPAN) (pure arithmetic, no GPU needed; n = 0 sizes it for lsmr alone), 8-byte aligned. */
+#define MOGE_PANO_MAX_VIEWS 16
+#define MOGE_PANO_SPAN 1024                /* elements one workgroup sums in the solver's norms */
+#define MOGE_PANO_STATE_DOUBLES 64         /* the solver's device-side scalars */
+#define MOGE_PANO_MAX_PIXELS (1 << 29)     /* row indices of the system are int32 */
+/* split_panorama_image: image (H, W, 3) u8 (is_u8 = 1) or fp32 -> out (n, resolution, resolution, 3) of the same type.  Coordinates in fp64,
+ * bilinear weights and blend in fp32 in the host's expression order, constant-0 border; u8: rint (half-even), then clip. */
+int moge_pano_split(const void* image, int is_u8, int H, int W, const float* extrinsics, const float* intrinsics, int n, int resolution, void* out, void* stream);
+int moge_pano_merge_workspace(int width, int height, int n, int64_t* bytes);
+/* the system of one level: distance (n, vh, vw) fp32, masks (n, vh, vw) u8 -> b (M) fp64, rows (M) u8, seen (height, width) u8.  Two launches:
+ * the per-view warp (log per tap in fp64 rounded once to fp32, replicated border, nearest mask), then the masked means over the views in view
+ * order in fp32.  A masked-out sample takes no part whatever it holds (NaN, inf). */
+int moge_pano_system(int width, int height, const float* distance, const uint8_t* masks, int n, int vh, int vw, const float* extrinsics, const float* intrinsics,
+                     void* workspace, double* b, uint8_t* rows, uint8_t* seen, void* stream);
+/* scipy.sparse.linalg.lsmr(A, b, damp=0, atol, btol, conlim, maxiter, x0) in fp64 on the system above: x0 (N) or NULL, maxiter 0 = min(selected
+ * rows, N), x (N).  Six launches per iteration; the scalar recurrences and the stopping rule run on the device and every kernel of an iteration
+ * returns at once when the rule has held, so x is the iterate at which it first held.  The call enqueues `poll` iterations, reads the state
+ * back (the only synchronisation), and goes on while it says so, at most maxiter iterations in all.  info: HOST array of 8 doubles = istop
+ * (scipy's numbering), itn, normr, normar, normA, condA, normx, selected rows.  Fixed-order sums: two calls give the same bits, for any poll. */
+int moge_pano_lsmr(int width, int height, const double* b, const uint8_t* rows, const double* x0, double atol, double btol, double conlim, int maxiter, int poll,
+                   void* workspace, double* x, double* info, void* stream);
+/* cv2.resize INTER_LINEAR of an fp32 map (centre (i + 0.5) * scale - 0.5 in fp64, weights fp32, edges replicated) and panorama.py's
+ * _resize_nearest of a u8 map (index = int(i * scale), clipped) */
+int moge_pano_resize_bilinear(const float* src, int H, int W, int out_h, int out_w, float* dst, void* stream);
+int moge_pano_resize_nearest(const uint8_t* src, int H, int W, int out_h, int out_w, uint8_t* dst, void* stream);
+/* dst (n) fp64 = the fp32 logarithm of src (n) fp32: the solver's start from a resized coarse solution */
+int moge_pano_log(const float* src, int64_t n, double* dst, void* stream);
+/* x (H * W) fp64 not NULL: distance (H, W) fp32 = exp(x); points (H, W, 3) not NULL: points = distance * fp32(direction of the pixel) */
+int moge_pano_finish(const double* x, float* distance, int H, int W, float* points, void* stream);
+/* tests only: out = A in (transpose 0: in (N), out (M)) or A^T in (transpose 1: in (M), out (N)) for the masked operator above */
+int moge_test_pano_apply(int width, int height, const uint8_t* rows, int transpose, const double* in, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

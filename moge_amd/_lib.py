@@ -25,6 +25,7 @@ KC_NAMES = ["gemm", "attn", "conv", "norm", "pre", "post", "recover", "gemm_pp"]
 ABI_VERSION = 5
 MESH_MAX_MAPS, MESH_BLOCK_PX, MESH_SCAN_SPAN, MESH_NO_FACES = 8, 1024, 256, -1       # include/moge_hip.h MOGE_MESH_*
 MESH_F32, MESH_U8, MESH_UV = 0, 1, 2                                                  # moge_mesh_dtype
+PANO_MAX_VIEWS, PANO_SPAN, PANO_STATE_DOUBLES, PANO_MAX_PIXELS = 16, 1024, 64, 1 << 29  # include/moge_hip.h MOGE_PANO_*
 
 
 class MogeConfig(C.Structure):
@@ -189,6 +190,15 @@ def _load(path: str = LIB_PATH, mode: int = C.RTLD_GLOBAL) -> C.CDLL:
         "moge_image_mesh_workspace": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
         "moge_image_mesh_count": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
         "moge_image_mesh_fill": (C.c_int, [i32, i32, i32, vp, C.POINTER(MeshMap), i32, i32, vp, vp, vp]),
+        "moge_pano_split": (C.c_int, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
+        "moge_pano_merge_workspace": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
+        "moge_pano_system": (C.c_int, [i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "moge_pano_lsmr": (C.c_int, [i32, i32, vp, vp, vp, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp, vp]),
+        "moge_pano_resize_bilinear": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
+        "moge_pano_resize_nearest": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
+        "moge_pano_log": (C.c_int, [vp, i64, vp, vp]),
+        "moge_pano_finish": (C.c_int, [vp, vp, i32, i32, vp, vp]),
+        "moge_test_pano_apply": (C.c_int, [i32, i32, vp, i32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the .so does not export what the header declares
@@ -225,7 +235,9 @@ EXPORTS = ["moge_abi_version", "moge_last_error", "moge_create", "moge_create_v1
            "moge_eval_lanczos_workspace", "moge_eval_lanczos", "moge_eval_masked_nearest", "moge_eval_resize_nearest", "moge_eval_remap",
            "moge_eval_quantile_cut", "moge_eval_unproject",
            "moge_refine_depth_workspace", "moge_refine_depth",
-           "moge_image_mesh_workspace", "moge_image_mesh_count", "moge_image_mesh_fill"]
+           "moge_image_mesh_workspace", "moge_image_mesh_count", "moge_image_mesh_fill",
+           "moge_pano_split", "moge_pano_merge_workspace", "moge_pano_system", "moge_pano_lsmr", "moge_pano_resize_bilinear", "moge_pano_resize_nearest",
+           "moge_pano_log", "moge_pano_finish", "moge_test_pano_apply"]
 
 
 def check(code: int) -> None:

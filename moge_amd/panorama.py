@@ -174,17 +174,13 @@ def _difference_operators(width: int, height: int):
     return Dx, Dy, lap.tocsr()
 
 
-def merge_panorama_depth(width: int, height: int, distance_maps: Sequence[np.ndarray], pred_masks: Sequence[np.ndarray], extrinsics: Sequence[np.ndarray],
-                         intrinsics: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
-    """panorama.py:109-191 -> (panorama distance (height, width) float32, panorama mask).  Coarse to fine: above 256 pixels the half-size
-    solution (resized) is the starting point of the solver."""
+def merge_system(width: int, height: int, distance_maps: Sequence[np.ndarray], pred_masks: Sequence[np.ndarray], extrinsics: Sequence[np.ndarray],
+                 intrinsics: Sequence[np.ndarray]):
+    """The least-squares system of ONE level of `merge_panorama_depth` (panorama.py:113-186), every stage of it: -> (bx, by, bl, rx, ry, rl, seen, A, b).
+    bx (height, width), by (height - 1, width), bl (height, width): the means over the views of the wrapped right difference, the lower
+    difference and the 5-point Laplacian of the warped log-distances; rx, ry, rl: flat masks of the equations some view supports; seen: the
+    panorama mask; A (float64 csr), b: the selected equations, in the order x, y, the column-0 y equations once more, Laplacian."""
     import scipy.sparse as sp
-    from scipy.sparse.linalg import lsmr
-
-    init = None
-    if max(width, height) > 256:
-        coarse, _ = merge_panorama_depth(width // 2, height // 2, distance_maps, pred_masks, extrinsics, intrinsics)
-        init = _resize_bilinear(coarse, height, width)
 
     directions = spherical_uv_to_directions(_uv_grid(height, width))
     n = len(distance_maps)
@@ -222,6 +218,21 @@ def merge_panorama_depth(width: int, height: int, distance_maps: Sequence[np.nda
     ry0 = ry[col0]
     A = sp.vstack([Dx[rx], Dy[ry], Dy[col0[ry0]], Lap[rl]], format="csr").astype(np.float64)          # (float64: lsmr's norm estimates overflow in float32)
     b = np.concatenate([bx.reshape(-1)[rx], by.reshape(-1)[ry], by.reshape(-1)[col0[ry0]], bl.reshape(-1)[rl]]).astype(np.float64)
+    return bx, by, bl, rx, ry, rl, seen, A, b
+
+
+def merge_panorama_depth(width: int, height: int, distance_maps: Sequence[np.ndarray], pred_masks: Sequence[np.ndarray], extrinsics: Sequence[np.ndarray],
+                         intrinsics: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
+    """panorama.py:109-191 -> (panorama distance (height, width) float32, panorama mask).  Coarse to fine: above 256 pixels the half-size
+    solution (resized) is the starting point of the solver."""
+    from scipy.sparse.linalg import lsmr
+
+    init = None
+    if max(width, height) > 256:
+        coarse, _ = merge_panorama_depth(width // 2, height // 2, distance_maps, pred_masks, extrinsics, intrinsics)
+        init = _resize_bilinear(coarse, height, width)
+
+    *_, seen, A, b = merge_system(width, height, distance_maps, pred_masks, extrinsics, intrinsics)
     x0 = None if init is None else np.log(init).reshape(-1).astype(np.float64)
     x = lsmr(A, b, atol=1e-5, btol=1e-5, x0=x0, show=False)[0]
     return np.exp(x).reshape(height, width).astype(np.float32), seen

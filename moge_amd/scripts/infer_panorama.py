@@ -13,7 +13,9 @@ differs from its own `scripts/infer.py` in two places - :132 writes `points` thr
 R, G, B = z, y, x) and :147 passes the mesh builder's uvs unflipped (`infer.py:148` flips v) - and whether the second one shows as a mirrored texture depends on
 the un-vendored utils3d / trimesh conventions; `--reference_compat` reproduces both byte conventions for callers that parse the reference's files.  The mesh is built on the GPU by
 `moge_amd.mesh.build_mesh_from_map` (points, image and the cleaned mask go up, the compacted arrays come back); `--host_mesh` keeps the numpy path of
-`moge_amd.io.build_mesh_from_map`, and both write the same bytes."""
+`moge_amd.io.build_mesh_from_map`, and both write the same bytes.  `--gpu_merge` (opt-in) runs split, merge, resize and points on the GPU as well
+(`moge_amd.panorama_gpu`): image, distance, mask and points stay on the device until a writer needs them, and the mesh step takes
+them from there; the default stays the host merge of `moge_amd.panorama`."""
 from __future__ import annotations
 
 import itertools
@@ -43,8 +45,9 @@ import numpy as np
 @click.option("--reference_compat", "reference_compat", is_flag=True,
               help="Write points.exr (R, G, B = z, y, x) and the GLB uvs (unflipped) exactly as the reference's panorama script does; default: the conventions of `moge infer`.")
 @click.option("--host_mesh", "host_mesh", is_flag=True, help="Build the mesh on the host (numpy) instead of the GPU; the files are the same.")
+@click.option("--gpu_merge", "gpu_merge", is_flag=True, help="Split the panorama and merge the views on the GPU (moge_amd.panorama_gpu) instead of the host; default: the host merge.")
 def main(input_path, output_path, pretrained_model_name_or_path, model_version, device_name, use_fp16, resize_to, resolution_level, threshold,
-         batch_size, save_splitted, save_maps_, save_glb_, save_ply_, show, reference_compat=False, host_mesh=False):
+         batch_size, save_splitted, save_maps_, save_glb_, save_ply_, show, reference_compat=False, host_mesh=False, gpu_merge=False):
     import torch
     from PIL import Image
 
@@ -52,6 +55,7 @@ def main(input_path, output_path, pretrained_model_name_or_path, model_version, 
     from moge_amd.mesh import UV, build_mesh_from_map as device_mesh_from_map
     from moge_amd.model import import_model_class_by_version
     from moge_amd.panorama import infer_panorama
+    from moge_amd.panorama_gpu import infer_panorama as infer_panorama_gpu
 
     suffices = ["jpg", "png", "jpeg", "JPG", "PNG", "JPEG"]
     if Path(input_path).is_dir():
@@ -80,8 +84,14 @@ def main(input_path, output_path, pretrained_model_name_or_path, model_version, 
         H, W = image.shape[:2]
         # (`--resolution_level` is accepted and NOT forwarded: the reference calls `model.infer(image_tensor, fov_x=fov_x, apply_mask=False)` with the
         #  model's default, moge/scripts/infer_panorama.py:101)
-        out = infer_panorama(model, image, resolution=512, batch_size=batch_size, merge_size=(1920, 960))
-        depth, mask, points = out["distance"], out["mask"], out["points"]
+        if gpu_merge:                                   # everything stays on the device; the writers below fetch what they write
+            image_t = torch.from_numpy(image).to(model.device)
+            out_t = infer_panorama_gpu(model, image_t, resolution=512, batch_size=batch_size, merge_size=(1920, 960))
+            wanted = (["distance", "mask", "points"] if save_maps_ or host_mesh else []) + (["views", "view_distance", "view_mask"] if save_splitted else [])
+            out = {k: out_t[k].cpu().numpy() for k in wanted}
+        else:
+            out = infer_panorama(model, image, resolution=512, batch_size=batch_size, merge_size=(1920, 960))
+        depth, mask, points = out.get("distance"), out.get("mask"), out.get("points")
         save_path = Path(output_path, p.relative_to(root).parent, p.stem)
         save_path.mkdir(exist_ok=True, parents=True)
         if save_splitted:
@@ -99,9 +109,14 @@ def main(input_path, output_path, pretrained_model_name_or_path, model_version, 
             save_exr(save_path / "points.exr", points[..., ::-1] if reference_compat else points)
             Image.fromarray((mask * 255).astype(np.uint8)).save(save_path / "mask.png")
         if save_glb_ or save_ply_:
-            cleaned = model.depth_edge_mask(torch.from_numpy(depth)[None], torch.from_numpy(mask)[None], rtol=threshold)[0]
+            if gpu_merge:
+                cleaned = model.depth_edge_mask(out_t["distance"][None], out_t["mask"][None], rtol=threshold)[0]
+            else:
+                cleaned = model.depth_edge_mask(torch.from_numpy(depth)[None], torch.from_numpy(mask)[None], rtol=threshold)[0]
             if host_mesh:
                 faces, vertices, vertex_colors, vertex_uvs = build_mesh_from_map(points, image.astype(np.float32) / 255, uv_map(H, W), mask=cleaned.cpu().numpy(), tri=True)
+            elif gpu_merge:
+                faces, vertices, vertex_colors, vertex_uvs = (t.cpu().numpy() for t in device_mesh_from_map(out_t["points"], image_t, UV, mask=cleaned, tri=True))
             else:                                       # this command does not flip the vertices on either path; the uvs are flipped below, on the compacted array
                 dev = cleaned.device
                 faces, vertices, vertex_colors, vertex_uvs = (t.cpu().numpy() for t in device_mesh_from_map(
