@@ -235,7 +235,7 @@ int moge_depth_edge_mask(moge_handle* h, const float* depth, const unsigned char
 
 /* replaces the per-key `.half()` of MoGeModel.forward on a half model (moge/model/v2.py:386-387): n fp32 values -> fp16
  * (round to nearest even, as torch), so that forward() too returns without a torch op between the kernels and the caller. */
-int moge_cast_f16(const float* src, void* dst_f16, int64_t n, void* stream);      /* stateless: runs on the current device */
+int moge_cast_f16(const float* src, void* dst_f16, int64_t n, void* stream);      /* stateless: see "Stateless entry points" below */
 
 /* Synchronise `stream` and report the sticky device-side status of the calls since the last sync
  * (MOGE_ERR_NONFINITE if a recovery solve saw non-finite residuals). */
@@ -395,6 +395,12 @@ int moge_test_resize_bilinear_uv(int precision, const float* x, float* out, int 
                                  float v0, float v1, void* stream);
 /* scripts/infer.py:98: uint8 (B,H,W,3) -> (B,3,H,W) = image / 255 in `precision` storage, returned as fp32 */
 int moge_test_u8_ingest(int precision, const uint8_t* in, float* out, int B, int H, int W, void* stream);
+
+/* ==== Stateless entry points: everything below that takes no handle, and moge_cast_f16 above =========================================
+ * A stateless entry runs on the device that is current on the calling thread when it is called: the caller makes the device of `stream`
+ * current first (hipSetDevice; the Python mirrors do it in moge_amd/_lib.py `on(dev)`), where the handle-based entries do that themselves.
+ * Every pointer belongs to that device unless its prototype says host.  Work is queued on `stream` and the call returns without waiting for
+ * it unless stated.  A non-zero return has its text in moge_last_error(), read on the thread that made the call. */
 
 /* ---- optimal-alignment solvers of the evaluation path (reference: moge/utils/alignment.py, called by moge/test/metrics.py:128-282) -------
  * Stateless (no handle); every pointer is device memory; results are written asynchronously on `stream`.

@@ -106,101 +106,105 @@ class MogeError(RuntimeError):
     pass
 
 
+_vp, _i32, _i64, _f32p = C.c_void_p, C.c_int, C.c_int64, C.c_void_p
+# every export of include/moge_hip.h: name -> (restype, argtypes).  tests/test_cabi_cpu.py pins the keys to the header.
+SIGNATURES = {
+    "moge_abi_version": (C.c_int, []),
+    "moge_last_error": (C.c_char_p, []),
+    "moge_create": (C.c_int, [C.POINTER(MogeConfig), _i32, C.POINTER(_vp)]),
+    "moge_create_v1": (C.c_int, [C.POINTER(MogeV1Config), _i32, C.POINTER(_vp)]),
+    "moge_v1_forward": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(Outputs), _vp]),
+    "moge_v1_infer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, C.POINTER(Outputs), _vp]),
+    "moge_destroy": (None, [_vp]),
+    "moge_load_weights": (C.c_int, [_vp, C.POINTER(TensorDesc), _i32, _vp]),
+    "moge_alloc_master": (C.c_int, [_vp]),
+    "moge_master_blob": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
+    "moge_master_ready": (C.c_int, [_vp]),
+    "moge_broadcast_weights": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "moge_set_precision": (C.c_int, [_vp, _i32, _vp]),
+    "moge_set_onnx_compatible_mode": (C.c_int, [_vp, _i32]),
+    "moge_workspace_bytes": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_size_t)]),
+    "moge_forward": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(Outputs), _vp]),
+    "moge_infer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, C.POINTER(Outputs), _vp]),
+    "moge_postprocess": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, C.POINTER(Outputs), _vp]),
+    "moge_depth_edge_mask": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp]),
+    "moge_cast_f16": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    "moge_sync": (C.c_int, [_vp, _vp]),
+    "moge_profile_enable": (C.c_int, [_vp, _i32]),
+    "moge_profile_read": (C.c_int, [_vp, C.POINTER(Profile), _i32]),
+    "moge_debug_tap": (C.c_int, [_vp, C.c_char_p, _vp, _i64, C.POINTER(_i64), _vp]),
+    "moge_tune_set": (None, [C.c_char_p, _i32]),
+    "moge_test_gemm": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_gemm_ex": (C.c_int, [C.POINTER(TestGemmArgs), _vp]),
+    "moge_test_layernorm": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _vp]),
+    "moge_test_attention": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _vp]),
+    "moge_test_conv3x3": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_conv_ex": (C.c_int, [C.POINTER(TestConvArgs), _vp]),
+    "moge_test_convt2x2": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_ct3": (C.c_int, [C.POINTER(TestCt3Args), _vp]),
+    "moge_test_preprocess": (C.c_int, [_f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_preprocess_ex": (C.c_int, [_i32, _i32, _f32p, _f32p, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_resize_bicubic_aa": (C.c_int, [_f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_resize_bicubic_aa_ex": (C.c_int, [_i32, _f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_groupnorm_relu": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_norm_act": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_posembed": (C.c_int, [_f32p, _f32p, _i32, _i32, _i32, _vp]),
+    "moge_test_posembed_ex": (C.c_int, [_f32p, _f32p, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_recover": (C.c_int, [_f32p, _vp, _f32p, _i32, _i32, _i32, _f32p, _f32p, _vp, _vp]),
+    "moge_test_head_final": (C.c_int, [C.POINTER(TestHeadArgs), _vp]),
+    "moge_test_head_final_dot": (C.c_int, [_i32, _i32, _f32p, _f32p, _i32, _i32, _f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_mlp_layer": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_layernorm_ex": (C.c_int, [_i32, _i32, _f32p, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_test_ln_raw": (C.c_int, [_f32p, _f32p, _f32p, _i32, _i32, _vp]),
+    "moge_test_ln_finalize": (C.c_int, [_f32p, _f32p, _i32, _i32, _i32, _vp]),
+    "moge_test_fold_ln": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _vp]),
+    "moge_test_resize_bilinear_uv": (C.c_int, [_i32, _f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
+    "moge_test_u8_ingest": (C.c_int, [_i32, _vp, _f32p, _i32, _i32, _i32, _vp]),
+    "moge_align_l1": (C.c_int, [_f32p, _f32p, _f32p, _i32, _i32, C.c_float, _f32p, _f32p, _vp, _vp]),
+    "moge_align_l1_anchored": (C.c_int, [_f32p, _f32p, _f32p, _i32, _i32, _i32, _vp, _vp, _i32, C.c_float, _f32p, _f32p, _vp, _vp]),
+    "moge_align_trunc_workspace": (C.c_int, [_i32, _i32, C.POINTER(_i64)]),
+    "moge_align_trunc": (C.c_int, [_f32p, _f32p, _f32p, _i32, _i32, C.c_float, C.c_float, _vp, _f32p, _f32p, _vp, _vp]),
+    "moge_align_trunc_anchored": (C.c_int, [_f32p, _f32p, _f32p, _i32, _i32, _i32, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _f32p, _f32p, _vp, _vp]),
+    "moge_align_select": (C.c_int, [_f32p, _vp, _i32, _i32, _f32p, _vp, _vp]),
+    "moge_align_lstsq": (C.c_int, [_f32p, _f32p, _f32p, _i32, _i32, _f32p, _f32p, _vp]),
+    "moge_metrics_lr_sample": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "moge_metrics_error": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "moge_metrics_masked_max": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "moge_metrics_boundary": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "moge_metrics_segment_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "moge_metrics_segment_pack": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "moge_metrics_segment_error": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "moge_eval_lanczos_workspace": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp]),
+    "moge_eval_lanczos": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "moge_eval_masked_nearest": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
+    "moge_eval_resize_nearest": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "moge_eval_remap": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32p, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "moge_eval_quantile_cut": (C.c_int, [_vp, _vp, _i32, C.c_float, C.c_float, C.c_float, _i32, _vp, _vp, _vp]),
+    "moge_eval_unproject": (C.c_int, [_vp, _vp, _i32, _i32, _f32p, _vp, _vp, _vp]),
+    "moge_refine_depth_workspace": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "moge_refine_depth": (C.c_int, [_f32p, _f32p, _f32p, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _f32p, _vp]),
+    "moge_image_mesh_workspace": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "moge_image_mesh_count": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "moge_image_mesh_fill": (C.c_int, [_i32, _i32, _i32, _vp, C.POINTER(MeshMap), _i32, _i32, _vp, _vp, _vp]),
+    "moge_pano_split": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "moge_pano_merge_workspace": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "moge_pano_system": (C.c_int, [_i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "moge_pano_lsmr": (C.c_int, [_i32, _i32, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "moge_pano_resize_bilinear": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "moge_pano_resize_nearest": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "moge_pano_log": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "moge_pano_finish": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "moge_test_pano_apply": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+}
+EXPORTS = list(SIGNATURES)
+
+
 def _load(path: str = LIB_PATH, mode: int = C.RTLD_GLOBAL) -> C.CDLL:
     if not os.path.exists(path):
         raise ImportError(f"{path} is missing: build it with `python -m moge_amd.build` (hipcc, gfx950). "
                           "moge_amd has no CPU / PyTorch fallback.")
     lib = C.CDLL(path, mode=mode)
-    vp, i32, i64, f32p = C.c_void_p, C.c_int, C.c_int64, C.c_void_p
-    sig = {
-        "moge_abi_version": (C.c_int, []),
-        "moge_last_error": (C.c_char_p, []),
-        "moge_create": (C.c_int, [C.POINTER(MogeConfig), i32, C.POINTER(vp)]),
-        "moge_create_v1": (C.c_int, [C.POINTER(MogeV1Config), i32, C.POINTER(vp)]),
-        "moge_v1_forward": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Outputs), vp]),
-        "moge_v1_infer": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(Outputs), vp]),
-        "moge_destroy": (None, [vp]),
-        "moge_load_weights": (C.c_int, [vp, C.POINTER(TensorDesc), i32, vp]),
-        "moge_alloc_master": (C.c_int, [vp]),
-        "moge_master_blob": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
-        "moge_master_ready": (C.c_int, [vp]),
-        "moge_broadcast_weights": (C.c_int, [vp, vp, i32, vp]),
-        "moge_set_precision": (C.c_int, [vp, i32, vp]),
-        "moge_set_onnx_compatible_mode": (C.c_int, [vp, i32]),
-        "moge_workspace_bytes": (C.c_int, [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_size_t)]),
-        "moge_forward": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Outputs), vp]),
-        "moge_infer": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(Outputs), vp]),
-        "moge_postprocess": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, C.POINTER(Outputs), vp]),
-        "moge_depth_edge_mask": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp]),
-        "moge_cast_f16": (C.c_int, [vp, vp, C.c_int64, vp]),
-        "moge_sync": (C.c_int, [vp, vp]),
-        "moge_profile_enable": (C.c_int, [vp, i32]),
-        "moge_profile_read": (C.c_int, [vp, C.POINTER(Profile), i32]),
-        "moge_debug_tap": (C.c_int, [vp, C.c_char_p, vp, i64, C.POINTER(i64), vp]),
-        "moge_tune_set": (None, [C.c_char_p, i32]),
-        "moge_test_gemm": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, i32, i32, vp]),
-        "moge_test_gemm_ex": (C.c_int, [C.POINTER(TestGemmArgs), vp]),
-        "moge_test_layernorm": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, vp]),
-        "moge_test_attention": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, i32, vp]),
-        "moge_test_conv3x3": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, vp]),
-        "moge_test_conv_ex": (C.c_int, [C.POINTER(TestConvArgs), vp]),
-        "moge_test_convt2x2": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, vp]),
-        "moge_test_ct3": (C.c_int, [C.POINTER(TestCt3Args), vp]),
-        "moge_test_preprocess": (C.c_int, [f32p, f32p, i32, i32, i32, i32, i32, vp]),
-        "moge_test_preprocess_ex": (C.c_int, [i32, i32, f32p, f32p, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
-        "moge_test_resize_bicubic_aa": (C.c_int, [f32p, f32p, i32, i32, i32, i32, i32, vp]),
-        "moge_test_resize_bicubic_aa_ex": (C.c_int, [i32, f32p, f32p, i32, i32, i32, i32, i32, i32, vp]),
-        "moge_test_groupnorm_relu": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, vp]),
-        "moge_test_norm_act": (C.c_int, [i32, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),
-        "moge_test_posembed": (C.c_int, [f32p, f32p, i32, i32, i32, vp]),
-        "moge_test_posembed_ex": (C.c_int, [f32p, f32p, i32, i32, i32, i32, vp]),
-        "moge_test_recover": (C.c_int, [f32p, vp, f32p, i32, i32, i32, f32p, f32p, vp, vp]),
-        "moge_test_head_final": (C.c_int, [C.POINTER(TestHeadArgs), vp]),
-        "moge_test_head_final_dot": (C.c_int, [i32, i32, f32p, f32p, i32, i32, f32p, f32p, i32, i32, i32, i32, i32, vp]),
-        "moge_test_mlp_layer": (C.c_int, [f32p, f32p, f32p, f32p, i32, i32, i32, i32, vp]),
-        "moge_test_layernorm_ex": (C.c_int, [i32, i32, f32p, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, vp]),
-        "moge_test_ln_raw": (C.c_int, [f32p, f32p, f32p, i32, i32, vp]),
-        "moge_test_ln_finalize": (C.c_int, [f32p, f32p, i32, i32, i32, vp]),
-        "moge_test_fold_ln": (C.c_int, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, vp]),
-        "moge_test_resize_bilinear_uv": (C.c_int, [i32, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
-        "moge_test_u8_ingest": (C.c_int, [i32, vp, f32p, i32, i32, i32, vp]),
-        "moge_align_l1": (C.c_int, [f32p, f32p, f32p, i32, i32, C.c_float, f32p, f32p, vp, vp]),
-        "moge_align_l1_anchored": (C.c_int, [f32p, f32p, f32p, i32, i32, i32, vp, vp, i32, C.c_float, f32p, f32p, vp, vp]),
-        "moge_align_trunc_workspace": (C.c_int, [i32, i32, C.POINTER(i64)]),
-        "moge_align_trunc": (C.c_int, [f32p, f32p, f32p, i32, i32, C.c_float, C.c_float, vp, f32p, f32p, vp, vp]),
-        "moge_align_trunc_anchored": (C.c_int, [f32p, f32p, f32p, i32, i32, i32, vp, vp, i32, C.c_float, C.c_float, vp, f32p, f32p, vp, vp]),
-        "moge_align_select": (C.c_int, [f32p, vp, i32, i32, f32p, vp, vp]),
-        "moge_align_lstsq": (C.c_int, [f32p, f32p, f32p, i32, i32, f32p, f32p, vp]),
-        "moge_metrics_lr_sample": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp]),
-        "moge_metrics_error": (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
-        "moge_metrics_masked_max": (C.c_int, [vp, vp, i32, vp, vp, vp]),
-        "moge_metrics_boundary": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
-        "moge_metrics_segment_stats": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]),
-        "moge_metrics_segment_pack": (C.c_int, [vp, i32, vp, vp, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
-        "moge_metrics_segment_error": (C.c_int, [vp, vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
-        "moge_eval_lanczos_workspace": (C.c_int, [i32, i32, i32, i32, vp, vp]),
-        "moge_eval_lanczos": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
-        "moge_eval_masked_nearest": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp]),
-        "moge_eval_resize_nearest": (C.c_int, [vp, i32, i32, i32, i32, i32, vp, vp]),
-        "moge_eval_remap": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp]),
-        "moge_eval_quantile_cut": (C.c_int, [vp, vp, i32, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp]),
-        "moge_eval_unproject": (C.c_int, [vp, vp, i32, i32, f32p, vp, vp, vp]),
-        "moge_refine_depth_workspace": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
-        "moge_refine_depth": (C.c_int, [f32p, f32p, f32p, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, f32p, vp]),
-        "moge_image_mesh_workspace": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
-        "moge_image_mesh_count": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
-        "moge_image_mesh_fill": (C.c_int, [i32, i32, i32, vp, C.POINTER(MeshMap), i32, i32, vp, vp, vp]),
-        "moge_pano_split": (C.c_int, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
-        "moge_pano_merge_workspace": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
-        "moge_pano_system": (C.c_int, [i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
-        "moge_pano_lsmr": (C.c_int, [i32, i32, vp, vp, vp, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp, vp]),
-        "moge_pano_resize_bilinear": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
-        "moge_pano_resize_nearest": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
-        "moge_pano_log": (C.c_int, [vp, i64, vp, vp]),
-        "moge_pano_finish": (C.c_int, [vp, vp, i32, i32, vp, vp]),
-        "moge_test_pano_apply": (C.c_int, [i32, i32, vp, i32, vp, vp, vp]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the .so does not export what the header declares
         fn.restype = res
         fn.argtypes = args
@@ -220,24 +224,6 @@ def experiments_lib() -> C.CDLL:
     if _experiments_lib is None:
         _experiments_lib = _load(EXPERIMENTS_LIB_PATH, C.RTLD_LOCAL)
     return _experiments_lib
-EXPORTS = ["moge_abi_version", "moge_last_error", "moge_create", "moge_create_v1", "moge_v1_forward", "moge_v1_infer", "moge_destroy", "moge_load_weights", "moge_alloc_master",
-           "moge_master_blob", "moge_master_ready", "moge_broadcast_weights", "moge_set_precision", "moge_set_onnx_compatible_mode", "moge_workspace_bytes", "moge_forward", "moge_infer",
-           "moge_postprocess", "moge_depth_edge_mask", "moge_cast_f16", "moge_sync", "moge_profile_enable", "moge_profile_read", "moge_debug_tap", "moge_tune_set", "moge_test_gemm",
-           "moge_test_gemm_ex", "moge_test_layernorm", "moge_test_attention", "moge_test_conv3x3", "moge_test_conv_ex", "moge_test_convt2x2", "moge_test_ct3", "moge_test_preprocess",
-           "moge_test_resize_bicubic_aa", "moge_test_groupnorm_relu", "moge_test_norm_act", "moge_test_posembed", "moge_test_recover",
-           "moge_test_head_final", "moge_test_head_final_dot", "moge_test_mlp_layer", "moge_test_layernorm_ex", "moge_test_ln_raw", "moge_test_ln_finalize",
-           "moge_test_fold_ln", "moge_test_resize_bilinear_uv", "moge_test_u8_ingest",
-           "moge_test_preprocess_ex", "moge_test_posembed_ex", "moge_test_resize_bicubic_aa_ex",
-           "moge_align_l1", "moge_align_l1_anchored", "moge_align_trunc_workspace", "moge_align_trunc", "moge_align_trunc_anchored",
-           "moge_align_select", "moge_align_lstsq",
-           "moge_metrics_lr_sample", "moge_metrics_error", "moge_metrics_masked_max", "moge_metrics_boundary", "moge_metrics_segment_stats",
-           "moge_metrics_segment_pack", "moge_metrics_segment_error",
-           "moge_eval_lanczos_workspace", "moge_eval_lanczos", "moge_eval_masked_nearest", "moge_eval_resize_nearest", "moge_eval_remap",
-           "moge_eval_quantile_cut", "moge_eval_unproject",
-           "moge_refine_depth_workspace", "moge_refine_depth",
-           "moge_image_mesh_workspace", "moge_image_mesh_count", "moge_image_mesh_fill",
-           "moge_pano_split", "moge_pano_merge_workspace", "moge_pano_system", "moge_pano_lsmr", "moge_pano_resize_bilinear", "moge_pano_resize_nearest",
-           "moge_pano_log", "moge_pano_finish", "moge_test_pano_apply"]
 
 
 def check(code: int) -> None:
@@ -256,6 +242,49 @@ def tune(key: str, value: int) -> None:
 
 def stream_ptr(device=None) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
+
+
+# ---- how a stateless op (moge_align_* ... moge_pano_*) is called: the contract is "Stateless entry points" in include/moge_hip.h ----
+def ptr(t):
+    """A tensor's data pointer as a C argument; None -> NULL."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def device_of(module: str, *tensors, host: str = None, tensors_only: bool = False) -> torch.device:
+    """The one device of an op's tensors (None entries skipped), for `moge_amd.<module>`.  A tensor off the GPU raises RuntimeError (`host`
+    names the module that has the host form), tensors on two GPUs raise ValueError; tensors_only: so does anything that is not a torch.Tensor."""
+    dev = None
+    for t in tensors:
+        if t is None:
+            continue
+        if tensors_only and not isinstance(t, torch.Tensor):
+            raise ValueError(f"expected torch tensors, got {type(t).__name__}")
+        if not t.is_cuda:
+            raise RuntimeError(f"moge_amd.{module} works on GPU tensors only (no CPU path{f': {host} is the host form' if host else ''})")
+        if dev is None:
+            dev = t.device
+        elif t.device != dev:
+            raise ValueError(f"moge_amd.{module} needs its tensors on one device, got {dev} and {t.device}")
+    if dev is None:
+        raise ValueError(f"moge_amd.{module}: no tensor to take the device from")
+    return dev
+
+
+class on:
+    """`with on(dev) as st:` makes `dev` current around the C calls of a stateless op (torch.cuda.device) and yields their stream argument: dev's
+    current stream, so a surrounding torch.cuda.stream(s) is honoured.  No host synchronisation.  A class, not a generator: this runs once per
+    C call of the evaluation path, where a sample takes a third of a millisecond."""
+    __slots__ = ("dev", "guard")
+
+    def __init__(self, dev):
+        self.dev, self.guard = dev, torch.cuda.device(dev)
+
+    def __enter__(self) -> int:
+        self.guard.__enter__()
+        return stream_ptr(self.dev)
+
+    def __exit__(self, *exc):
+        return self.guard.__exit__(*exc)
 
 
 class DevView:

@@ -26,22 +26,9 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib as L
+from ._lib import ptr
 
 MAX_ROW = 15360          # residuals per row (csrc/alignment.hip: a row is sorted inside one CU's LDS)
-
-
-def _need_cuda(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("moge_amd.alignment works on GPU tensors only (no CPU path)")
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _trunc_value(trunc) -> float:
@@ -70,15 +57,16 @@ def align(x: torch.Tensor, y: torch.Tensor, w: torch.Tensor, trunc=None, eps: fl
     """alignment.py:52-89: min_a sum_i w_i |a x_i - y_i| per row of the broadcast (..., n) inputs -> a (...), loss (...), index (...) (int64).
     With trunc: NotImplementedError, use align_trunc."""
     _no_trunc(trunc)
-    _need_cuda(x, y, w)
+    dev = L.device_of("alignment", x, y, w)
     x, y, w = torch.broadcast_tensors(x, y, w)
     bshape, n = x.shape[:-1], x.shape[-1]
     x, y, w = (t.reshape(-1, n).float().contiguous() for t in (x, y, w))
     rows = x.shape[0]
-    a = torch.empty(rows, device=x.device, dtype=torch.float32)
+    a = torch.empty(rows, device=dev, dtype=torch.float32)
     loss = torch.empty_like(a)
-    index = torch.empty(rows, device=x.device, dtype=torch.int32)
-    L.check(L.lib.moge_align_l1(_p(x), _p(y), _p(w), rows, n, eps, _p(a), _p(loss), _p(index), _stream()))
+    index = torch.empty(rows, device=dev, dtype=torch.int32)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_align_l1(ptr(x), ptr(y), ptr(w), rows, n, eps, ptr(a), ptr(loss), ptr(index), st))
     return a.reshape(bshape), loss.reshape(bshape), index.long().reshape(bshape)
 
 
@@ -87,17 +75,18 @@ def align_trunc(x: torch.Tensor, y: torch.Tensor, w: torch.Tensor, trunc, eps: f
     inputs -> a (...), loss (...), index (...) (int64).  The kernel picks the element; `a` is gathered outside no_grad as in the reference (:139),
     so it is differentiable."""
     trunc = _trunc_value(trunc)
-    _need_cuda(x, y, w)
+    dev = L.device_of("alignment", x, y, w)
     x, y, w = torch.broadcast_tensors(x, y, w)
     bshape, n = x.shape[:-1], x.shape[-1]
     x, y, w = x.reshape(-1, n), y.reshape(-1, n), w.reshape(-1, n)
     xk, yk, wk = (t.detach().float().contiguous() for t in (x, y, w))
     rows = xk.shape[0]
-    ws = _trunc_workspace(n, rows, xk.device)
-    a = torch.empty(rows, device=x.device, dtype=torch.float32)
+    ws = _trunc_workspace(n, rows, dev)
+    a = torch.empty(rows, device=dev, dtype=torch.float32)
     loss = torch.empty_like(a)
-    index = torch.empty(rows, device=x.device, dtype=torch.int32)
-    L.check(L.lib.moge_align_trunc(_p(xk), _p(yk), _p(wk), rows, n, trunc, eps, _p(ws), _p(a), _p(loss), _p(index), _stream()))
+    index = torch.empty(rows, device=dev, dtype=torch.int32)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_align_trunc(ptr(xk), ptr(yk), ptr(wk), rows, n, trunc, eps, ptr(ws), ptr(a), ptr(loss), ptr(index), st))
     index = index.long()
     sign = torch.sign(x)
     xs, ys = x * sign, y * sign                                                             # :94-95
@@ -109,23 +98,25 @@ def _anchor_search(src: torch.Tensor, tgt: torch.Tensor, weight: torch.Tensor, c
     """src / tgt (B, n, d), weight (B, n): one solve per sample with weight > 0 (alignment.py:184 / :269 / :324), then the best anchor per batch
     element (alignment.py:197 / :284 / :339).  -> anchor sample (B,), solution element (B,) in [0, n*d)"""
     B, n, d = src.shape
+    dev = src.device
     ab, an = torch.where(weight > 0)
     rows = ab.numel()
     if rows == 0:
         raise ValueError("no sample with weight > 0")
     rb, rk = ab.int().contiguous(), an.int().contiguous()
-    scale = torch.empty(rows, device=src.device, dtype=torch.float32)
+    scale = torch.empty(rows, device=dev, dtype=torch.float32)
     loss = torch.empty_like(scale)
-    index = torch.empty(rows, device=src.device, dtype=torch.int32)
-    if trunc is None:
-        L.check(L.lib.moge_align_l1_anchored(_p(src), _p(tgt), _p(weight), n, d, comp_mask, _p(rb), _p(rk), rows, 1e-7, _p(scale), _p(loss), _p(index), _stream()))
-    else:
-        ws = _trunc_workspace(n * d, rows, src.device)
-        L.check(L.lib.moge_align_trunc_anchored(_p(src), _p(tgt), _p(weight), n, d, comp_mask, _p(rb), _p(rk), rows, trunc, 1e-7, _p(ws), _p(scale), _p(loss),
-                                                _p(index), _stream()))
-    min_loss = torch.empty(B, device=src.device, dtype=torch.float32)
-    min_row = torch.empty(B, device=src.device, dtype=torch.int32)
-    L.check(L.lib.moge_align_select(_p(loss), _p(rb), rows, B, _p(min_loss), _p(min_row), _stream()))
+    index = torch.empty(rows, device=dev, dtype=torch.int32)
+    min_loss = torch.empty(B, device=dev, dtype=torch.float32)
+    min_row = torch.empty(B, device=dev, dtype=torch.int32)
+    ws = _trunc_workspace(n * d, rows, dev) if trunc is not None else None
+    with L.on(dev) as st:
+        if trunc is None:
+            L.check(L.lib.moge_align_l1_anchored(ptr(src), ptr(tgt), ptr(weight), n, d, comp_mask, ptr(rb), ptr(rk), rows, 1e-7, ptr(scale), ptr(loss), ptr(index), st))
+        else:
+            L.check(L.lib.moge_align_trunc_anchored(ptr(src), ptr(tgt), ptr(weight), n, d, comp_mask, ptr(rb), ptr(rk), rows, trunc, 1e-7, ptr(ws), ptr(scale), ptr(loss),
+                                                    ptr(index), st))
+        L.check(L.lib.moge_align_select(ptr(loss), ptr(rb), rows, B, ptr(min_loss), ptr(min_row), st))
     sel = min_row.long()
     if bool((sel < 0).any()):
         raise ValueError("a batch element has no sample with weight > 0")       # the reference indexes with -1 here (last anchor of the batch)
@@ -145,7 +136,7 @@ def align_depth_scale(depth_src: torch.Tensor, depth_tgt: torch.Tensor, weight: 
 def align_depth_affine(depth_src: torch.Tensor, depth_tgt: torch.Tensor, weight: Optional[torch.Tensor], trunc=None):
     """alignment.py:163-212: (..., n) -> scale (...), shift (...)"""
     trunc = None if trunc is None else _trunc_value(trunc)
-    _need_cuda(depth_src, depth_tgt, weight)
+    L.device_of("alignment", depth_src, depth_tgt, weight)
     bshape, n = depth_src.shape[:-1], depth_src.shape[-1]
     src, tgt, w = (t.reshape(-1, n).float().contiguous() for t in (depth_src, depth_tgt, weight))
     i1, i2 = _anchor_search(src[..., None].detach(), tgt[..., None].detach(), w, 0b1, trunc)
@@ -162,7 +153,7 @@ def align_points_scale(points_src: torch.Tensor, points_tgt: torch.Tensor, weigh
 
 
 def _points_anchor_solve(points_src, points_tgt, weight, comp_mask: int, trunc=None):
-    _need_cuda(points_src, points_tgt, weight)
+    L.device_of("alignment", points_src, points_tgt, weight)
     bshape, n = points_src.shape[:-2], points_src.shape[-2]
     src, tgt, w = points_src.reshape(-1, n, 3).float().contiguous(), points_tgt.reshape(-1, n, 3).float().contiguous(), weight.reshape(-1, n).float().contiguous()
     B = src.shape[0]
@@ -201,12 +192,13 @@ def align_points_xyz_shift(points_src: torch.Tensor, points_tgt: torch.Tensor, w
 
 def align_affine_lstsq(x: torch.Tensor, y: torch.Tensor, w: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """alignment.py:399-415: least-squares (a, b) of sqrt(w) x a + b ~ sqrt(w) y per row of (..., N)."""
-    _need_cuda(x, y, w)
+    dev = L.device_of("alignment", x, y, w)
     bshape, n = x.shape[:-1], x.shape[-1]
     xs, ys = x.reshape(-1, n).float().contiguous(), y.reshape(-1, n).float().contiguous()
     ws = w.reshape(-1, n).float().contiguous() if w is not None else None
     rows = xs.shape[0]
-    a = torch.empty(rows, device=x.device, dtype=torch.float32)
+    a = torch.empty(rows, device=dev, dtype=torch.float32)
     b = torch.empty_like(a)
-    L.check(L.lib.moge_align_lstsq(_p(xs), _p(ys), _p(ws), rows, n, _p(a), _p(b), _stream()))
+    with L.on(dev) as st:
+        L.check(L.lib.moge_align_lstsq(ptr(xs), ptr(ys), ptr(ws), rows, n, ptr(a), ptr(b), st))
     return a.reshape(bshape), b.reshape(bshape)

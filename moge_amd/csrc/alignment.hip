@@ -473,17 +473,13 @@ __global__ __launch_bounds__(TPR * RPW) void align_trunc_kernel(const AlignArgs 
 // ------------------------------------------------------------------------------------------------------------------------
 static int align_launch(const AlignArgs& g, int rows, int NE, hipStream_t st) {
     if (rows <= 0) return 0;
-    if (NE < 1 || NE > ALIGN_MAX_N) {
-        moge_internal_set_error("moge_align_l1: a row holds 1 .. 15360 residuals (the row is sorted inside one CU's LDS)");
-        return MOGE_ERR_INVALID;
-    }
+    if (NE < 1 || NE > ALIGN_MAX_N) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_l1: a row holds 1 .. 15360 residuals (the row is sorted inside one CU's LDS)");
     int NP = ALIGN_THREADS;                              // at least one element per thread keeps the scan simple
     while (NP < NE) NP <<= 1;
     const size_t smem = (size_t)NP * 4 + (size_t)NE * 4 + (size_t)NP * 2;
-    if (int rc = set_dyn_lds<align_l1_kernel>((int)smem)) { moge_internal_set_error("moge_align_l1: cannot reserve LDS"); return MOGE_ERR_HIP; }
+    if (int rc = set_dyn_lds<align_l1_kernel>((int)smem)) return moge_internal_fail(MOGE_ERR_HIP, "moge_align_l1: cannot reserve LDS");
     hipLaunchKernelGGL(align_l1_kernel, dim3((unsigned)rows), dim3(ALIGN_THREADS), smem, st, g, NE, NP);
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_align_l1: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    return launched("moge_align_l1: launch failed");
 }
 
 // the row's path and workspace: 0 = four rows of one wave per workgroup in LDS, 1 = one 1024-thread workgroup per row in LDS, 2 = global scratch
@@ -497,12 +493,7 @@ static int trunc_plan(int NE, TruncLayout& lay) {
 }
 
 static int trunc_check_n(int NE, const char* who) {
-    if (NE < 1 || NE > ALIGN_MAX_N) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: a row holds 1 .. %d residuals, got %d", who, ALIGN_MAX_N, NE);
-        moge_internal_set_error(msg);
-        return MOGE_ERR_INVALID;
-    }
+    if (NE < 1 || NE > ALIGN_MAX_N) return moge_internal_fail(MOGE_ERR_INVALID, "%s: a row holds 1 .. %d residuals, got %d", who, ALIGN_MAX_N, NE);
     return 0;
 }
 
@@ -513,28 +504,26 @@ static int trunc_launch(const AlignArgs& g, int rows, int NE, float trunc, void*
     const int path = trunc_plan(NE, lay);
     if (path == 0) {
         constexpr auto k = align_trunc_kernel<TRUNC_SMALL_TPR, TRUNC_SMALL_RPW, true>;
-        if (set_dyn_lds<k>(TRUNC_LDS_BYTES)) { moge_internal_set_error("moge_align_trunc: cannot reserve LDS"); return MOGE_ERR_HIP; }
-        const int blocks = (rows + TRUNC_SMALL_RPW - 1) / TRUNC_SMALL_RPW;
-        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(TRUNC_SMALL_TPR * TRUNC_SMALL_RPW), (size_t)lay.bytes * TRUNC_SMALL_RPW, st, g, rows, trunc,
+        if (set_dyn_lds<k>(TRUNC_LDS_BYTES)) return moge_internal_fail(MOGE_ERR_HIP, "moge_align_trunc: cannot reserve LDS");
+        hipLaunchKernelGGL(k, dim3(blocks(rows, TRUNC_SMALL_RPW)), dim3(TRUNC_SMALL_TPR * TRUNC_SMALL_RPW), (size_t)lay.bytes * TRUNC_SMALL_RPW, st, g, rows, trunc,
                            lay, (char*)nullptr);
     } else if (path == 1) {
         constexpr auto k = align_trunc_kernel<ALIGN_THREADS, 1, true>;
-        if (set_dyn_lds<k>(TRUNC_LDS_BYTES)) { moge_internal_set_error("moge_align_trunc: cannot reserve LDS"); return MOGE_ERR_HIP; }
+        if (set_dyn_lds<k>(TRUNC_LDS_BYTES)) return moge_internal_fail(MOGE_ERR_HIP, "moge_align_trunc: cannot reserve LDS");
         hipLaunchKernelGGL(k, dim3((unsigned)rows), dim3(ALIGN_THREADS), (size_t)lay.bytes, st, g, rows, trunc, lay, (char*)nullptr);
     } else {
-        if (!workspace) { moge_internal_set_error("moge_align_trunc: this row length needs the workspace of moge_align_trunc_workspace"); return MOGE_ERR_INVALID; }
-        const int blocks = rows < TRUNC_SLOTS ? rows : TRUNC_SLOTS;
-        hipLaunchKernelGGL((align_trunc_kernel<ALIGN_THREADS, 1, false>), dim3((unsigned)blocks), dim3(ALIGN_THREADS), 0, st, g, rows, trunc, lay,
+        if (!workspace) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_trunc: this row length needs the workspace of moge_align_trunc_workspace");
+        const int slots = rows < TRUNC_SLOTS ? rows : TRUNC_SLOTS;
+        hipLaunchKernelGGL((align_trunc_kernel<ALIGN_THREADS, 1, false>), dim3((unsigned)slots), dim3(ALIGN_THREADS), 0, st, g, rows, trunc, lay,
                            (char*)workspace);
     }
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_align_trunc: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    return launched("moge_align_trunc: launch failed");
 }
 
 extern "C" {
 
 int moge_align_trunc_workspace(int n, int rows, int64_t* bytes) {
-    if (!bytes) { moge_internal_set_error("moge_align_trunc_workspace: null argument"); return MOGE_ERR_INVALID; }
+    if (!bytes) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_trunc_workspace: null argument");
     *bytes = 0;
     if (int rc = trunc_check_n(n, "moge_align_trunc_workspace")) return rc;
     TruncLayout lay;
@@ -544,7 +533,7 @@ int moge_align_trunc_workspace(int n, int rows, int64_t* bytes) {
 
 int moge_align_trunc(const float* x, const float* y, const float* w, int rows, int n, float trunc, float eps, void* workspace, float* a, float* loss,
                      int32_t* index, void* stream) {
-    if (!x || !y || !w || !a || !loss || !index) { moge_internal_set_error("moge_align_trunc: null argument"); return MOGE_ERR_INVALID; }
+    if (!x || !y || !w || !a || !loss || !index) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_trunc: null argument");
     AlignArgs g{};
     g.x = x; g.y = y; g.w = w; g.n = n; g.d = 1; g.eps = eps; g.a = a; g.loss = loss; g.index = index;
     return trunc_launch(g, rows, n, trunc, workspace, (hipStream_t)stream);
@@ -553,8 +542,8 @@ int moge_align_trunc(const float* x, const float* y, const float* w, int rows, i
 int moge_align_trunc_anchored(const float* src, const float* tgt, const float* weight, int n, int d, int comp_mask, const int32_t* row_batch,
                               const int32_t* row_anchor, int rows, float trunc, float eps, void* workspace, float* scale, float* loss, int32_t* index,
                               void* stream) {
-    if (!src || !tgt || !weight || !row_batch || !row_anchor || !scale || !loss || !index) { moge_internal_set_error("moge_align_trunc_anchored: null argument"); return MOGE_ERR_INVALID; }
-    if (d != 1 && d != 3) { moge_internal_set_error("moge_align_trunc_anchored: d must be 1 (depth) or 3 (points)"); return MOGE_ERR_INVALID; }
+    if (!src || !tgt || !weight || !row_batch || !row_anchor || !scale || !loss || !index) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_trunc_anchored: null argument");
+    if (d != 1 && d != 3) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_trunc_anchored: d must be 1 (depth) or 3 (points)");
     AlignArgs g{};
     g.src = src; g.tgt = tgt; g.wt = weight; g.row_b = row_batch; g.row_k = row_anchor;
     g.n = n; g.d = d; g.comp_mask = comp_mask; g.eps = eps; g.a = scale; g.loss = loss; g.index = index;
@@ -562,7 +551,7 @@ int moge_align_trunc_anchored(const float* src, const float* tgt, const float* w
 }
 
 int moge_align_l1(const float* x, const float* y, const float* w, int rows, int n, float eps, float* a, float* loss, int32_t* index, void* stream) {
-    if (!x || !y || !w || !a || !loss || !index) { moge_internal_set_error("moge_align_l1: null argument"); return MOGE_ERR_INVALID; }
+    if (!x || !y || !w || !a || !loss || !index) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_l1: null argument");
     AlignArgs g{};
     g.x = x; g.y = y; g.w = w; g.n = n; g.d = 1; g.eps = eps; g.a = a; g.loss = loss; g.index = index;
     return align_launch(g, rows, n, (hipStream_t)stream);
@@ -570,8 +559,8 @@ int moge_align_l1(const float* x, const float* y, const float* w, int rows, int 
 
 int moge_align_l1_anchored(const float* src, const float* tgt, const float* weight, int n, int d, int comp_mask, const int32_t* row_batch,
                            const int32_t* row_anchor, int rows, float eps, float* scale, float* loss, int32_t* index, void* stream) {
-    if (!src || !tgt || !weight || !row_batch || !row_anchor || !scale || !loss || !index) { moge_internal_set_error("moge_align_l1_anchored: null argument"); return MOGE_ERR_INVALID; }
-    if (d != 1 && d != 3) { moge_internal_set_error("moge_align_l1_anchored: d must be 1 (depth) or 3 (points)"); return MOGE_ERR_INVALID; }
+    if (!src || !tgt || !weight || !row_batch || !row_anchor || !scale || !loss || !index) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_l1_anchored: null argument");
+    if (d != 1 && d != 3) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_l1_anchored: d must be 1 (depth) or 3 (points)");
     AlignArgs g{};
     g.src = src; g.tgt = tgt; g.wt = weight; g.row_b = row_batch; g.row_k = row_anchor;
     g.n = n; g.d = d; g.comp_mask = comp_mask; g.eps = eps; g.a = scale; g.loss = loss; g.index = index;
@@ -579,17 +568,17 @@ int moge_align_l1_anchored(const float* src, const float* tgt, const float* weig
 }
 
 int moge_align_select(const float* loss, const int32_t* row_batch, int rows, int batch, float* min_loss, int32_t* min_row, void* stream) {
-    if (!loss || !row_batch || !min_loss || !min_row) { moge_internal_set_error("moge_align_select: null argument"); return MOGE_ERR_INVALID; }
+    if (!loss || !row_batch || !min_loss || !min_row) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_select: null argument");
     if (batch <= 0) return 0;
     hipLaunchKernelGGL(align_select_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, loss, row_batch, rows, min_loss, min_row);
-    return hipGetLastError() == hipSuccess ? 0 : MOGE_ERR_HIP;
+    return launched("moge_align_select: launch failed");
 }
 
 int moge_align_lstsq(const float* x, const float* y, const float* w, int rows, int n, float* a, float* b, void* stream) {
-    if (!x || !y || !a || !b || n < 2) { moge_internal_set_error("moge_align_lstsq: null argument or fewer than two samples"); return MOGE_ERR_INVALID; }
+    if (!x || !y || !a || !b || n < 2) return moge_internal_fail(MOGE_ERR_INVALID, "moge_align_lstsq: null argument or fewer than two samples");
     if (rows <= 0) return 0;
     hipLaunchKernelGGL(align_lstsq_kernel, dim3((unsigned)rows), dim3(1024), 0, (hipStream_t)stream, x, y, w, n, a, b);
-    return hipGetLastError() == hipSuccess ? 0 : MOGE_ERR_HIP;
+    return launched("moge_align_lstsq: launch failed");
 }
 
 }   // extern "C"

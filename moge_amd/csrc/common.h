@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "../../include/moge_hip.h"
 
 typedef _Float16 f16;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -291,7 +292,15 @@ inline int pp_device_cus() {
 // host-side launchers (gemm.hip, gemm_pp.hip)
 template <typename T> int launch_gemm(const GemmArgs& g, int amode, hipStream_t st);
 bool gemm_pp_eligible(const GemmArgs& g);
-void moge_internal_set_error(const char* msg);      // model.hip: text behind moge_last_error()
+// model.hip: sets the calling thread's text behind moge_last_error() and returns `code`, so a failed check is one `return`
+int moge_internal_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// after the launches of a stateless entry point: reads hipGetLastError() once; `what` is the whole message ("<entry>: launch failed")
+inline int launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : moge_internal_fail(MOGE_ERR_HIP, "%s (%s)", what, hipGetErrorString(e));
+}
+// grid size: workgroups of `per` elements that cover n
+inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 bool gemm_fuses_ln_finalize(const GemmArgs& g);      // launch_gemm<f16>(g, AMODE_LINEAR) will take gemm_glds_kernel, which can finalise the LN statistics itself (GemmArgs::ln_mr_out)
 bool gemm_runs_pp(const GemmArgs& g);       // launch_gemm<f16>(g, AMODE_LINEAR) will take the ping-pong throughput kernel (profiler class)
 int launch_gemm_pp(const GemmArgs& g, hipStream_t st);

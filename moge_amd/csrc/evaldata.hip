@@ -22,13 +22,6 @@ constexpr int EV_BLOCKS = 512;                  // grid of the grid-stride passe
 constexpr int PRECISION_BITS = 32 - 8 - 2;      // Pillow Resample.c
 constexpr int EV_SEG_BINS = MOGE_EVAL_SEG_BINS;
 
-static int ev_launched(const char* what) {
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error(what); return MOGE_ERR_HIP; }
-    return 0;
-}
-
-static inline unsigned ev_grid(long long n) { return (unsigned)((n + EV_THREADS - 1) / EV_THREADS); }
-
 // ------------------------------------------------------------------------------------------------------------------------
 // Lanczos (Pillow Resample.c).  precompute_coeffs: scale = in / out, filterscale = max(scale, 1), support = 3 filterscale,
 // ksize = 2 ceil(support) + 1; per output index the window [xmin, xmin + xmax) with xmin = (int)(center - support + 0.5) >= 0,
@@ -359,18 +352,18 @@ __global__ __launch_bounds__(EV_THREADS) void unproject_kernel(float* depth, uin
 extern "C" {
 
 int moge_eval_lanczos_workspace(int H, int W, int out_h, int out_w, int64_t* tmp_bytes, int64_t* coeff_ints) {
-    if (!tmp_bytes || !coeff_ints || H < 1 || W < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_lanczos_workspace: bad argument"); return MOGE_ERR_INVALID; }
+    if (!tmp_bytes || !coeff_ints || H < 1 || W < 1 || out_h < 1 || out_w < 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_lanczos_workspace: bad argument");
     *tmp_bytes = (int64_t)H * out_w * 3;
     *coeff_ints = (int64_t)out_w * (2 + lz_ksize(W, out_w)) + (int64_t)out_h * (2 + lz_ksize(H, out_h));
     return 0;
 }
 
 int moge_eval_lanczos(const uint8_t* src, int H, int W, int out_h, int out_w, uint8_t* tmp, int32_t* coeffs, uint8_t* out, void* stream) {
-    if (!src || !out || !tmp || !coeffs) { moge_internal_set_error("moge_eval_lanczos: null argument"); return MOGE_ERR_INVALID; }
-    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_lanczos: empty image"); return MOGE_ERR_INVALID; }
+    if (!src || !out || !tmp || !coeffs) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_lanczos: null argument");
+    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_lanczos: empty image");
     hipStream_t st = (hipStream_t)stream;
     if (H == out_h && W == out_w) {                     // Image.resize returns a copy when the size is unchanged
-        if (hipMemcpyAsync(out, src, (size_t)H * W * 3, hipMemcpyDeviceToDevice, st) != hipSuccess) { moge_internal_set_error("moge_eval_lanczos: copy failed"); return MOGE_ERR_HIP; }
+        if (hipMemcpyAsync(out, src, (size_t)H * W * 3, hipMemcpyDeviceToDevice, st) != hipSuccess) return moge_internal_fail(MOGE_ERR_HIP, "moge_eval_lanczos: copy failed");
         return 0;
     }
     const int kh = lz_ksize(W, out_w), kv = lz_ksize(H, out_h);
@@ -379,10 +372,10 @@ int moge_eval_lanczos(const uint8_t* src, int H, int W, int out_h, int out_w, ui
     int32_t* bv = kkh + (size_t)out_w * kh;
     int32_t* kkv = bv + 2 * (size_t)out_h;
     const bool need_h = W != out_w, need_v = H != out_h;
-    hipLaunchKernelGGL(lz_coeff_kernel, dim3(ev_grid(out_w)), dim3(EV_THREADS), 0, st, W, out_w, kh, bh, kkh);
-    if (int rc = ev_launched("moge_eval_lanczos: coefficient launch failed")) return rc;
-    hipLaunchKernelGGL(lz_coeff_kernel, dim3(ev_grid(out_h)), dim3(EV_THREADS), 0, st, H, out_h, kv, bv, kkv);
-    if (int rc = ev_launched("moge_eval_lanczos: coefficient launch failed")) return rc;
+    hipLaunchKernelGGL(lz_coeff_kernel, dim3(blocks(out_w, EV_THREADS)), dim3(EV_THREADS), 0, st, W, out_w, kh, bh, kkh);
+    if (int rc = launched("moge_eval_lanczos: coefficient launch failed")) return rc;
+    hipLaunchKernelGGL(lz_coeff_kernel, dim3(blocks(out_h, EV_THREADS)), dim3(EV_THREADS), 0, st, H, out_h, kv, bv, kkv);
+    if (int rc = launched("moge_eval_lanczos: coefficient launch failed")) return rc;
     // rows the vertical pass reads: [first, last) from the host-side copy of the same bounds arithmetic
     int first = 0, last = H;
     if (need_v) {
@@ -398,76 +391,76 @@ int moge_eval_lanczos(const uint8_t* src, int H, int W, int out_h, int out_w, ui
     if (need_h) {
         const int rows = last - first;
         uint8_t* dst = need_v ? tmp : out;
-        hipLaunchKernelGGL(lz_horizontal_kernel, dim3(ev_grid((long long)rows * out_w)), dim3(EV_THREADS), 0, st, src, W, first, rows, out_w, kh, bh, kkh, dst);
-        if (int rc = ev_launched("moge_eval_lanczos: horizontal launch failed")) return rc;
+        hipLaunchKernelGGL(lz_horizontal_kernel, dim3(blocks((long long)rows * out_w, EV_THREADS)), dim3(EV_THREADS), 0, st, src, W, first, rows, out_w, kh, bh, kkh, dst);
+        if (int rc = launched("moge_eval_lanczos: horizontal launch failed")) return rc;
     }
     if (need_v) {
         const uint8_t* vin = need_h ? tmp : src;
         const int shift = need_h ? first : 0;
-        hipLaunchKernelGGL(lz_vertical_kernel, dim3(ev_grid((long long)out_h * out_w)), dim3(EV_THREADS), 0, st, vin, out_w, out_h, kv, bv, shift, kkv, out);
-        if (int rc = ev_launched("moge_eval_lanczos: vertical launch failed")) return rc;
+        hipLaunchKernelGGL(lz_vertical_kernel, dim3(blocks((long long)out_h * out_w, EV_THREADS)), dim3(EV_THREADS), 0, st, vin, out_w, out_h, kv, bv, shift, kkv, out);
+        if (int rc = launched("moge_eval_lanczos: vertical launch failed")) return rc;
     }
     return 0;
 }
 
 int moge_eval_masked_nearest(const float* depth, const uint8_t* mask, int H, int W, int out_h, int out_w, float fx, float fy, float cx, float cy,
                              float* out_depth, uint8_t* out_mask, float* distance, void* stream) {
-    if (!depth || !mask || !out_depth || !out_mask || !distance) { moge_internal_set_error("moge_eval_masked_nearest: null argument"); return MOGE_ERR_INVALID; }
-    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_masked_nearest: empty map"); return MOGE_ERR_INVALID; }
-    hipLaunchKernelGGL(masked_nearest_kernel, dim3(ev_grid((long long)out_h * out_w)), dim3(EV_THREADS), 0, (hipStream_t)stream, depth, mask, H, W, out_h,
+    if (!depth || !mask || !out_depth || !out_mask || !distance) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_masked_nearest: null argument");
+    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_masked_nearest: empty map");
+    hipLaunchKernelGGL(masked_nearest_kernel, dim3(blocks((long long)out_h * out_w, EV_THREADS)), dim3(EV_THREADS), 0, (hipStream_t)stream, depth, mask, H, W, out_h,
                        out_w, fx, fy, cx, cy, out_depth, out_mask, distance);
-    return ev_launched("moge_eval_masked_nearest: launch failed");
+    return launched("moge_eval_masked_nearest: launch failed");
 }
 
 int moge_eval_resize_nearest(const void* src, int elem_bytes, int H, int W, int out_h, int out_w, void* dst, void* stream) {
-    if (!src || !dst || (elem_bytes != 1 && elem_bytes != 2)) { moge_internal_set_error("moge_eval_resize_nearest: null argument or element size not 1 / 2"); return MOGE_ERR_INVALID; }
-    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_resize_nearest: empty map"); return MOGE_ERR_INVALID; }
-    hipLaunchKernelGGL(resize_nearest_kernel, dim3(ev_grid((long long)out_h * out_w)), dim3(EV_THREADS), 0, (hipStream_t)stream, src, elem_bytes, H, W,
+    if (!src || !dst || (elem_bytes != 1 && elem_bytes != 2)) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_resize_nearest: null argument or element size not 1 / 2");
+    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_resize_nearest: empty map");
+    hipLaunchKernelGGL(resize_nearest_kernel, dim3(blocks((long long)out_h * out_w, EV_THREADS)), dim3(EV_THREADS), 0, (hipStream_t)stream, src, elem_bytes, H, W,
                        out_h, out_w, dst);
-    return ev_launched("moge_eval_resize_nearest: launch failed");
+    return launched("moge_eval_resize_nearest: launch failed");
 }
 
 int moge_eval_remap(const uint8_t* image, const float* distance, const uint8_t* mask, const void* seg, int seg_bytes, int h, int w, int out_h, int out_w,
                     const float* mats, uint8_t* out_u8, float* out_chw, float* out_depth, uint8_t* out_mask, int32_t* out_seg, int32_t* seg_hist, void* stream) {
-    if (!image || !distance || !mask || !mats || !out_u8 || !out_chw || !out_depth || !out_mask) { moge_internal_set_error("moge_eval_remap: null argument"); return MOGE_ERR_INVALID; }
-    if (seg_bytes && (!seg || !out_seg || !seg_hist || (seg_bytes != 1 && seg_bytes != 2))) { moge_internal_set_error("moge_eval_remap: segmentation arguments"); return MOGE_ERR_INVALID; }
-    if (h < 1 || w < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_remap: empty map"); return MOGE_ERR_INVALID; }
+    if (!image || !distance || !mask || !mats || !out_u8 || !out_chw || !out_depth || !out_mask) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_remap: null argument");
+    if (seg_bytes && (!seg || !out_seg || !seg_hist || (seg_bytes != 1 && seg_bytes != 2))) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_remap: segmentation arguments");
+    if (h < 1 || w < 1 || out_h < 1 || out_w < 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_remap: empty map");
     hipStream_t st = (hipStream_t)stream;
     EvMats m;
     for (int i = 0; i < 9; i++) { m.T[i] = mats[i]; m.Ki[i] = mats[9 + i]; }
-    if (seg_bytes && hipMemsetAsync(seg_hist, 0, EV_SEG_BINS * sizeof(int32_t), st) != hipSuccess) { moge_internal_set_error("moge_eval_remap: memset failed"); return MOGE_ERR_HIP; }
-    hipLaunchKernelGGL(remap_kernel, dim3(ev_grid((long long)out_h * out_w)), dim3(EV_THREADS), 0, st, image, distance, mask, seg, seg_bytes, h, w, out_h, out_w,
+    if (seg_bytes && hipMemsetAsync(seg_hist, 0, EV_SEG_BINS * sizeof(int32_t), st) != hipSuccess) return moge_internal_fail(MOGE_ERR_HIP, "moge_eval_remap: memset failed");
+    hipLaunchKernelGGL(remap_kernel, dim3(blocks((long long)out_h * out_w, EV_THREADS)), dim3(EV_THREADS), 0, st, image, distance, mask, seg, seg_bytes, h, w, out_h, out_w,
                        m, out_u8, out_chw, out_depth, out_mask, out_seg, seg_hist);
-    return ev_launched("moge_eval_remap: launch failed");
+    return launched("moge_eval_remap: launch failed");
 }
 
 int moge_eval_quantile_cut(float* depth, uint8_t* mask, int n, float q, float drop_max_depth, float depth_unit, int has_unit, uint32_t* workspace,
                            int32_t* count, void* stream) {
-    if (!depth || !mask || !workspace || !count || n < 1) { moge_internal_set_error("moge_eval_quantile_cut: null argument or n < 1"); return MOGE_ERR_INVALID; }
-    if (!(q >= 0.f && q <= 1.f)) { moge_internal_set_error("moge_eval_quantile_cut: q outside [0, 1]"); return MOGE_ERR_INVALID; }
+    if (!depth || !mask || !workspace || !count || n < 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_quantile_cut: null argument or n < 1");
+    if (!(q >= 0.f && q <= 1.f)) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_quantile_cut: q outside [0, 1]");
     hipStream_t st = (hipStream_t)stream;
     uint32_t* state = workspace;
     uint32_t* hist = workspace + 8;
     if (hipMemsetAsync(workspace, 0, MOGE_EVAL_QUANTILE_WORKSPACE * sizeof(uint32_t), st) != hipSuccess ||
-        hipMemsetAsync(count, 0, sizeof(int32_t), st) != hipSuccess) { moge_internal_set_error("moge_eval_quantile_cut: memset failed"); return MOGE_ERR_HIP; }
+        hipMemsetAsync(count, 0, sizeof(int32_t), st) != hipSuccess) return moge_internal_fail(MOGE_ERR_HIP, "moge_eval_quantile_cut: memset failed");
     for (int pass = 0; pass < 4; pass++) {
         hipLaunchKernelGGL(q_hist_kernel, dim3(EV_BLOCKS), dim3(EV_THREADS), 0, st, depth, mask, n, pass, state, hist);
-        if (int rc = ev_launched("moge_eval_quantile_cut: histogram launch failed")) return rc;
+        if (int rc = launched("moge_eval_quantile_cut: histogram launch failed")) return rc;
         hipLaunchKernelGGL(q_select_kernel, dim3(1), dim3(64), 0, st, pass, q, drop_max_depth, state, hist);
-        if (int rc = ev_launched("moge_eval_quantile_cut: select launch failed")) return rc;
+        if (int rc = launched("moge_eval_quantile_cut: select launch failed")) return rc;
     }
     hipLaunchKernelGGL(q_apply_kernel, dim3(EV_BLOCKS), dim3(EV_THREADS), 0, st, depth, mask, n, state, depth_unit, has_unit, count);
-    return ev_launched("moge_eval_quantile_cut: apply launch failed");
+    return launched("moge_eval_quantile_cut: apply launch failed");
 }
 
 int moge_eval_unproject(float* depth, uint8_t* mask, int out_h, int out_w, const float* kinv, const int32_t* count, float* points, void* stream) {
-    if (!depth || !mask || !kinv || !count || !points) { moge_internal_set_error("moge_eval_unproject: null argument"); return MOGE_ERR_INVALID; }
-    if (out_h < 1 || out_w < 1) { moge_internal_set_error("moge_eval_unproject: empty map"); return MOGE_ERR_INVALID; }
+    if (!depth || !mask || !kinv || !count || !points) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_unproject: null argument");
+    if (out_h < 1 || out_w < 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_eval_unproject: empty map");
     EvKinv m;
     for (int i = 0; i < 9; i++) m.Ki[i] = kinv[i];
-    hipLaunchKernelGGL(unproject_kernel, dim3(ev_grid((long long)out_h * out_w)), dim3(EV_THREADS), 0, (hipStream_t)stream, depth, mask, out_h, out_w, m,
+    hipLaunchKernelGGL(unproject_kernel, dim3(blocks((long long)out_h * out_w, EV_THREADS)), dim3(EV_THREADS), 0, (hipStream_t)stream, depth, mask, out_h, out_w, m,
                        count, points);
-    return ev_launched("moge_eval_unproject: launch failed");
+    return launched("moge_eval_unproject: launch failed");
 }
 
 }  // extern "C"

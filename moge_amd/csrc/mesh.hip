@@ -47,8 +47,8 @@ struct MeshMaps { moge_mesh_map m[MOGE_MESH_MAX_MAPS]; int n; };
 static MeshWs mesh_ws(void* workspace, int B, int H, int W) {
     const int64_t N = (int64_t)H * W;
     MeshWs w;
-    w.nblk = (int)((N + MOGE_MESH_BLOCK_PX - 1) / MOGE_MESH_BLOCK_PX);
-    w.nspan = (w.nblk + MOGE_MESH_SCAN_SPAN - 1) / MOGE_MESH_SCAN_SPAN;
+    w.nblk = (int)blocks(N, MOGE_MESH_BLOCK_PX);
+    w.nspan = (int)blocks(w.nblk, MOGE_MESH_SCAN_SPAN);
     w.blk = (int2*)workspace;
     w.span = w.blk + (int64_t)B * w.nblk;
     w.img = w.span + (int64_t)B * w.nspan;
@@ -254,19 +254,15 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_faces_kernel(MeshWs ws, con
 // host
 // ------------------------------------------------------------------------------------------------------------------------
 static int mesh_check(int B, int H, int W, const char* who) {
-    if (B < 0 || B > 65535 || H < 1 || W < 1 || (int64_t)H * W > INT_MAX) {                // grid.y <= 65535; pixel indices are int32
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: need 0 <= B <= 65535, H >= 1, W >= 1 and H * W < 2^31, got B = %d, H = %d, W = %d", who, B, H, W);
-        moge_internal_set_error(msg);
-        return MOGE_ERR_INVALID;
-    }
+    if (B < 0 || B > 65535 || H < 1 || W < 1 || (int64_t)H * W > INT_MAX)                  // grid.y <= 65535; pixel indices are int32
+        return moge_internal_fail(MOGE_ERR_INVALID, "%s: need 0 <= B <= 65535, H >= 1, W >= 1 and H * W < 2^31, got B = %d, H = %d, W = %d", who, B, H, W);
     return 0;
 }
 
 extern "C" {
 
 int moge_image_mesh_workspace(int B, int H, int W, int64_t* bytes) {
-    if (!bytes) { moge_internal_set_error("moge_image_mesh_workspace: null argument"); return MOGE_ERR_INVALID; }
+    if (!bytes) return moge_internal_fail(MOGE_ERR_INVALID, "moge_image_mesh_workspace: null argument");
     *bytes = 0;
     if (int rc = mesh_check(B, H, W, "moge_image_mesh_workspace")) return rc;
     const MeshWs w = mesh_ws(nullptr, B, H, W);
@@ -276,7 +272,7 @@ int moge_image_mesh_workspace(int B, int H, int W, int64_t* bytes) {
 
 int moge_image_mesh_count(const uint8_t* mask, int B, int H, int W, int points, void* workspace, int32_t* counts, int64_t* offsets, void* stream) {
     if (int rc = mesh_check(B, H, W, "moge_image_mesh_count")) return rc;
-    if (!workspace || !counts || !offsets) { moge_internal_set_error("moge_image_mesh_count: null argument"); return MOGE_ERR_INVALID; }
+    if (!workspace || !counts || !offsets) return moge_internal_fail(MOGE_ERR_INVALID, "moge_image_mesh_count: null argument");
     if (B == 0) return 0;
     const MeshWs w = mesh_ws(workspace, B, H, W);
     hipStream_t st = (hipStream_t)stream;
@@ -284,28 +280,24 @@ int moge_image_mesh_count(const uint8_t* mask, int B, int H, int W, int points, 
     hipLaunchKernelGGL(mesh_span_scan_kernel, dim3((unsigned)w.nspan, (unsigned)B), dim3(MESH_THREADS), 0, st, w.blk, w.span, w.nblk, w.nspan);
     hipLaunchKernelGGL(mesh_image_scan_kernel, dim3((unsigned)B), dim3(64), 0, st, w.span, w.img, counts, w.nspan);
     hipLaunchKernelGGL(mesh_offsets_kernel, dim3(1), dim3(64), 0, st, w.img, offsets, B);
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_image_mesh_count: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    return launched("moge_image_mesh_count: launch failed");
 }
 
 int moge_image_mesh_fill(int B, int H, int W, void* workspace, const moge_mesh_map* maps, int n_maps, int tri, int32_t* faces, const int64_t* offsets,
                          void* stream) {
     if (int rc = mesh_check(B, H, W, "moge_image_mesh_fill")) return rc;
-    if (n_maps < 0 || n_maps > MOGE_MESH_MAX_MAPS) { moge_internal_set_error("moge_image_mesh_fill: n_maps must be 0 ... 8"); return MOGE_ERR_INVALID; }
-    if (tri != MOGE_MESH_NO_FACES && tri != 0 && tri != 1) { moge_internal_set_error("moge_image_mesh_fill: tri must be MOGE_MESH_NO_FACES, 0 or 1"); return MOGE_ERR_INVALID; }
-    if (!workspace || !offsets || (n_maps > 0 && !maps) || (tri != MOGE_MESH_NO_FACES && !faces)) {
-        moge_internal_set_error("moge_image_mesh_fill: null argument");
-        return MOGE_ERR_INVALID;
-    }
-    if (n_maps == 0 && tri == MOGE_MESH_NO_FACES) { moge_internal_set_error("moge_image_mesh_fill: nothing to write (no maps and no faces)"); return MOGE_ERR_INVALID; }
+    if (n_maps < 0 || n_maps > MOGE_MESH_MAX_MAPS) return moge_internal_fail(MOGE_ERR_INVALID, "moge_image_mesh_fill: n_maps must be 0 ... 8");
+    if (tri != MOGE_MESH_NO_FACES && tri != 0 && tri != 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_image_mesh_fill: tri must be MOGE_MESH_NO_FACES, 0 or 1");
+    if (!workspace || !offsets || (n_maps > 0 && !maps) || (tri != MOGE_MESH_NO_FACES && !faces)) return moge_internal_fail(MOGE_ERR_INVALID, "moge_image_mesh_fill: null argument");
+    if (n_maps == 0 && tri == MOGE_MESH_NO_FACES) return moge_internal_fail(MOGE_ERR_INVALID, "moge_image_mesh_fill: nothing to write (no maps and no faces)");
     MeshMaps mm{};
     mm.n = n_maps;
     for (int k = 0; k < n_maps; k++) {
         const moge_mesh_map& m = maps[k];
-        if (m.channels < 1 || m.channels > 4) { moge_internal_set_error("moge_image_mesh_fill: a map needs 1 ... 4 channels"); return MOGE_ERR_INVALID; }
-        if (m.dtype != MOGE_MESH_F32 && m.dtype != MOGE_MESH_U8 && m.dtype != MOGE_MESH_UV) { moge_internal_set_error("moge_image_mesh_fill: unknown map dtype"); return MOGE_ERR_INVALID; }
-        if (m.dtype == MOGE_MESH_UV && m.channels != 2) { moge_internal_set_error("moge_image_mesh_fill: the generated uv map has 2 channels"); return MOGE_ERR_INVALID; }
-        if (!m.out || (m.dtype != MOGE_MESH_UV && !m.data)) { moge_internal_set_error("moge_image_mesh_fill: null map pointer"); return MOGE_ERR_INVALID; }
+        if (m.channels < 1 || m.channels > 4) return moge_internal_fail(MOGE_ERR_INVALID, "moge_image_mesh_fill: a map needs 1 ... 4 channels");
+        if (m.dtype != MOGE_MESH_F32 && m.dtype != MOGE_MESH_U8 && m.dtype != MOGE_MESH_UV) return moge_internal_fail(MOGE_ERR_INVALID, "moge_image_mesh_fill: unknown map dtype");
+        if (m.dtype == MOGE_MESH_UV && m.channels != 2) return moge_internal_fail(MOGE_ERR_INVALID, "moge_image_mesh_fill: the generated uv map has 2 channels");
+        if (!m.out || (m.dtype != MOGE_MESH_UV && !m.data)) return moge_internal_fail(MOGE_ERR_INVALID, "moge_image_mesh_fill: null map pointer");
         mm.m[k] = m;
     }
     if (B == 0) return 0;
@@ -314,8 +306,7 @@ int moge_image_mesh_fill(int B, int H, int W, void* workspace, const moge_mesh_m
     const dim3 grid((unsigned)w.nblk, (unsigned)B);
     hipLaunchKernelGGL(mesh_vertices_kernel, grid, dim3(MESH_THREADS), 0, st, w, mm, offsets, H, W);
     if (tri != MOGE_MESH_NO_FACES) hipLaunchKernelGGL(mesh_faces_kernel, grid, dim3(MESH_THREADS), 0, st, w, offsets, H, W, tri, faces);
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_image_mesh_fill: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    return launched("moge_image_mesh_fill: launch failed");
 }
 
 }   // extern "C"

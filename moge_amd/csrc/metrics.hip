@@ -409,92 +409,86 @@ __global__ __launch_bounds__(MET_THREADS) void seg_error_kernel(const int* seg, 
 // ------------------------------------------------------------------------------------------------------------------------
 // C ABI (include/moge_hip.h)
 // ------------------------------------------------------------------------------------------------------------------------
-static int met_launched(const char* what) {
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error(what); return MOGE_ERR_HIP; }
-    return 0;
-}
-
 extern "C" {
 
 int moge_metrics_lr_sample(const uint8_t* mask, int H, int W, int out_h, int out_w, uint8_t* lr_mask, int32_t* lr_index, void* stream) {
-    if (!mask || !lr_mask || !lr_index) { moge_internal_set_error("moge_metrics_lr_sample: null argument"); return MOGE_ERR_INVALID; }
-    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) { moge_internal_set_error("moge_metrics_lr_sample: empty image or grid"); return MOGE_ERR_INVALID; }
+    if (!mask || !lr_mask || !lr_index) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_lr_sample: null argument");
+    if (H < 1 || W < 1 || out_h < 1 || out_w < 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_lr_sample: empty image or grid");
     const int no = out_h * out_w;
-    hipLaunchKernelGGL(lr_sample_kernel, dim3((no + MET_THREADS - 1) / MET_THREADS), dim3(MET_THREADS), 0, (hipStream_t)stream, mask, H, W, out_h, out_w,
+    hipLaunchKernelGGL(lr_sample_kernel, dim3(blocks(no, MET_THREADS)), dim3(MET_THREADS), 0, (hipStream_t)stream, mask, H, W, out_h, out_w,
                        lr_mask, lr_index);
-    return met_launched("moge_metrics_lr_sample: launch failed");
+    return launched("moge_metrics_lr_sample: launch failed");
 }
 
 int moge_metrics_error(const float* pred, const float* gt, const uint8_t* mask, int n, int dim, const float* params, int K, double* partials,
                        double* out, void* stream) {
-    if (!pred || !gt || !mask || !params || !partials || !out) { moge_internal_set_error("moge_metrics_error: null argument"); return MOGE_ERR_INVALID; }
-    if (n < 1 || (dim != 1 && dim != 3) || K < 1 || K > MET_MAX_K) { moge_internal_set_error("moge_metrics_error: n >= 1, dim 1 or 3, 1 <= K <= 8"); return MOGE_ERR_INVALID; }
+    if (!pred || !gt || !mask || !params || !partials || !out) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_error: null argument");
+    if (n < 1 || (dim != 1 && dim != 3) || K < 1 || K > MET_MAX_K) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_error: n >= 1, dim 1 or 3, 1 <= K <= 8");
     hipStream_t st = (hipStream_t)stream;
     if (dim == 1) hipLaunchKernelGGL(error_kernel<1>, dim3(MET_BLOCKS), dim3(MET_THREADS), 0, st, pred, gt, mask, n, params, K, partials);
     else hipLaunchKernelGGL(error_kernel<3>, dim3(MET_BLOCKS), dim3(MET_THREADS), 0, st, pred, gt, mask, n, params, K, partials);
-    if (int rc = met_launched("moge_metrics_error: launch failed")) return rc;
+    if (int rc = launched("moge_metrics_error: launch failed")) return rc;
     hipLaunchKernelGGL(met_final_kernel, dim3(1), dim3(MET_THREADS), 0, st, partials, K * 3, MET_BLOCKS, out);
-    return met_launched("moge_metrics_error: final launch failed");
+    return launched("moge_metrics_error: final launch failed");
 }
 
 int moge_metrics_masked_max(const float* x, const uint8_t* mask, int n, float* partials, float* out, void* stream) {
-    if (!x || !mask || !partials || !out || n < 1) { moge_internal_set_error("moge_metrics_masked_max: null argument or n < 1"); return MOGE_ERR_INVALID; }
+    if (!x || !mask || !partials || !out || n < 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_masked_max: null argument or n < 1");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(masked_max_kernel, dim3(MET_BLOCKS), dim3(MET_THREADS), 0, st, x, mask, n, partials);
-    if (int rc = met_launched("moge_metrics_masked_max: launch failed")) return rc;
+    if (int rc = launched("moge_metrics_masked_max: launch failed")) return rc;
     hipLaunchKernelGGL(masked_max_final_kernel, dim3(1), dim3(64), 0, st, partials, out);
-    return met_launched("moge_metrics_masked_max: final launch failed");
+    return launched("moge_metrics_masked_max: final launch failed");
 }
 
 int moge_metrics_boundary(const float* pred, const float* gt, const uint8_t* mask, int H, int W, int64_t* counts, void* stream) {
-    if (!pred || !gt || !mask || !counts) { moge_internal_set_error("moge_metrics_boundary: null argument"); return MOGE_ERR_INVALID; }
-    if (H < 1 || W < 1) { moge_internal_set_error("moge_metrics_boundary: empty image"); return MOGE_ERR_INVALID; }
+    if (!pred || !gt || !mask || !counts) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_boundary: null argument");
+    if (H < 1 || W < 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_boundary: empty image");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(counts, 0, BF_COUNTS * sizeof(int64_t), st) != hipSuccess) { moge_internal_set_error("moge_metrics_boundary: memset failed"); return MOGE_ERR_HIP; }
-    hipLaunchKernelGGL(boundary_kernel, dim3((W + BF_T - 1) / BF_T, (H + BF_T - 1) / BF_T), dim3(BF_T * BF_T), 0, st, pred, gt, mask, H, W,
+    if (hipMemsetAsync(counts, 0, BF_COUNTS * sizeof(int64_t), st) != hipSuccess) return moge_internal_fail(MOGE_ERR_HIP, "moge_metrics_boundary: memset failed");
+    hipLaunchKernelGGL(boundary_kernel, dim3(blocks(W, BF_T), blocks(H, BF_T)), dim3(BF_T * BF_T), 0, st, pred, gt, mask, H, W,
                        reinterpret_cast<unsigned long long*>(counts));
-    return met_launched("moge_metrics_boundary: launch failed");
+    return launched("moge_metrics_boundary: launch failed");
 }
 
 int moge_metrics_segment_stats(const int32_t* seg, const uint8_t* mask, const float* gt, int H, int W, const uint8_t* lr_mask, const int32_t* lr_index,
                                int out_h, int out_w, const int32_t* labels, int U, int32_t* bbox, int32_t* lr_count, float* diameter, void* stream) {
-    if (!seg || !mask || !gt || !lr_mask || !lr_index || !labels || !bbox || !lr_count || !diameter) { moge_internal_set_error("moge_metrics_segment_stats: null argument"); return MOGE_ERR_INVALID; }
-    if (H < 1 || W < 1 || out_h < 1 || out_w < 1 || U < 1 || U > MOGE_METRICS_MAX_SEGMENTS) { moge_internal_set_error("moge_metrics_segment_stats: bad sizes (1 <= U <= 512)"); return MOGE_ERR_INVALID; }
+    if (!seg || !mask || !gt || !lr_mask || !lr_index || !labels || !bbox || !lr_count || !diameter) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_segment_stats: null argument");
+    if (H < 1 || W < 1 || out_h < 1 || out_w < 1 || U < 1 || U > MOGE_METRICS_MAX_SEGMENTS) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_segment_stats: bad sizes (1 <= U <= 512)");
     hipStream_t st = (hipStream_t)stream;
-    const int ub = (U + MET_THREADS - 1) / MET_THREADS, NL = out_h * out_w;
+    const unsigned ub = blocks(U, MET_THREADS);
+    const int NL = out_h * out_w;
     hipLaunchKernelGGL(seg_init_kernel, dim3(ub), dim3(MET_THREADS), 0, st, U, bbox, lr_count);
     hipLaunchKernelGGL(seg_bbox_kernel, dim3(MET_BLOCKS), dim3(MET_THREADS), (size_t)U * 7 * 4, st, seg, mask, gt, H * W, labels, U, bbox);
-    hipLaunchKernelGGL(seg_lr_count_kernel, dim3((NL + MET_THREADS - 1) / MET_THREADS), dim3(MET_THREADS), 0, st, seg, W, lr_mask, lr_index, NL, labels, U, lr_count);
+    hipLaunchKernelGGL(seg_lr_count_kernel, dim3(blocks(NL, MET_THREADS)), dim3(MET_THREADS), 0, st, seg, W, lr_mask, lr_index, NL, labels, U, lr_count);
     hipLaunchKernelGGL(seg_diameter_kernel, dim3(ub), dim3(MET_THREADS), 0, st, bbox, U, diameter);
-    return met_launched("moge_metrics_segment_stats: launch failed");
+    return launched("moge_metrics_segment_stats: launch failed");
 }
 
 int moge_metrics_segment_pack(const int32_t* seg, int W, const uint8_t* lr_mask, const int32_t* lr_index, int out_h, int out_w, const int32_t* labels, int U,
                               const int32_t* kept, int E, int n_max, const float* pred, const float* gt, const float* diameter, float* src, float* tgt,
                               float* weight, void* stream) {
-    if (!seg || !lr_mask || !lr_index || !labels || !kept || !pred || !gt || !diameter || !src || !tgt || !weight) { moge_internal_set_error("moge_metrics_segment_pack: null argument"); return MOGE_ERR_INVALID; }
+    if (!seg || !lr_mask || !lr_index || !labels || !kept || !pred || !gt || !diameter || !src || !tgt || !weight) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_segment_pack: null argument");
     const int NL = out_h * out_w;
-    if (W < 1 || NL < 1 || U < 1 || U > MOGE_METRICS_MAX_SEGMENTS || E < 1 || E > U || n_max < 1 || n_max > NL || NL > 16384) { moge_internal_set_error("moge_metrics_segment_pack: bad sizes"); return MOGE_ERR_INVALID; }
-    hipLaunchKernelGGL(seg_pack_kernel, dim3((E + 63) / 64), dim3(64), (size_t)NL * 4, (hipStream_t)stream, seg, W, lr_mask, lr_index, NL, labels, U, kept, E, n_max,
+    if (W < 1 || NL < 1 || U < 1 || U > MOGE_METRICS_MAX_SEGMENTS || E < 1 || E > U || n_max < 1 || n_max > NL || NL > 16384) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_segment_pack: bad sizes");
+    hipLaunchKernelGGL(seg_pack_kernel, dim3(blocks(E, 64)), dim3(64), (size_t)NL * 4, (hipStream_t)stream, seg, W, lr_mask, lr_index, NL, labels, U, kept, E, n_max,
                        pred, gt, diameter, src, tgt, weight);
-    return met_launched("moge_metrics_segment_pack: launch failed");
+    return launched("moge_metrics_segment_pack: launch failed");
 }
 
 int moge_metrics_segment_error(const int32_t* seg, const uint8_t* mask, const float* pred, const float* gt, int n, const int32_t* labels, int U, const int32_t* row,
                                const int32_t* kept, int E, const float* scale, const float* shift, const float* diameter, double* partials, double* out, void* stream) {
-    if (!seg || !mask || !pred || !gt || !labels || !row || !kept || !scale || !shift || !diameter || !partials || !out) { moge_internal_set_error("moge_metrics_segment_error: null argument"); return MOGE_ERR_INVALID; }
-    if (n < 1 || U < 1 || U > MOGE_METRICS_MAX_SEGMENTS || E < 1 || E > U) { moge_internal_set_error("moge_metrics_segment_error: bad sizes (1 <= E <= U <= 512)"); return MOGE_ERR_INVALID; }
+    if (!seg || !mask || !pred || !gt || !labels || !row || !kept || !scale || !shift || !diameter || !partials || !out) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_segment_error: null argument");
+    if (n < 1 || U < 1 || U > MOGE_METRICS_MAX_SEGMENTS || E < 1 || E > U) return moge_internal_fail(MOGE_ERR_INVALID, "moge_metrics_segment_error: bad sizes (1 <= E <= U <= 512)");
     hipStream_t st = (hipStream_t)stream;
     const size_t smem = (size_t)MET_WAVES * E * 3 * 8 + (size_t)U * 2 * 4;
     // the attribute is set once per device: reserve the largest size any call can need
-    if (set_dyn_lds<seg_error_kernel>(MET_WAVES * MOGE_METRICS_MAX_SEGMENTS * 3 * 8 + MOGE_METRICS_MAX_SEGMENTS * 2 * 4)) {
-        moge_internal_set_error("moge_metrics_segment_error: cannot reserve LDS");
-        return MOGE_ERR_HIP;
-    }
+    if (set_dyn_lds<seg_error_kernel>(MET_WAVES * MOGE_METRICS_MAX_SEGMENTS * 3 * 8 + MOGE_METRICS_MAX_SEGMENTS * 2 * 4))
+        return moge_internal_fail(MOGE_ERR_HIP, "moge_metrics_segment_error: cannot reserve LDS");
     hipLaunchKernelGGL(seg_error_kernel, dim3(MET_BLOCKS), dim3(MET_THREADS), smem, st, seg, mask, pred, gt, n, labels, U, row, scale, shift, diameter, kept, E, partials);
-    if (int rc = met_launched("moge_metrics_segment_error: launch failed")) return rc;
-    hipLaunchKernelGGL(met_final_kernel, dim3((E * 3 + MET_THREADS - 1) / MET_THREADS), dim3(MET_THREADS), 0, st, partials, E * 3, MET_BLOCKS, out);
-    return met_launched("moge_metrics_segment_error: final launch failed");
+    if (int rc = launched("moge_metrics_segment_error: launch failed")) return rc;
+    hipLaunchKernelGGL(met_final_kernel, dim3(blocks(E * 3, MET_THREADS)), dim3(MET_THREADS), 0, st, partials, E * 3, MET_BLOCKS, out);
+    return launched("moge_metrics_segment_error: final launch failed");
 }
 
 }   // extern "C"

@@ -22,7 +22,7 @@
 // errors
 // ------------------------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int fail(int code, const char* fmt, ...) {
+int moge_internal_fail(int code, const char* fmt, ...) {       // common.h: the stateless entry points outside this file fail through it too
     char buf[1024];
     va_list ap;
     va_start(ap, fmt);
@@ -31,9 +31,8 @@ static int fail(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
-void moge_internal_set_error(const char* msg) { g_err = msg; }     // for the stateless entry points outside this file (alignment.hip)
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(MOGE_ERR_HIP, "%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-#define LCHK(x) do { int e_ = (x); if (e_ != 0) return fail(e_ < 0 ? MOGE_ERR_INVALID : MOGE_ERR_HIP, "%s: launch failed (%d: %s) (%s:%d)", #x, e_, e_ > 0 ? hipGetErrorString((hipError_t)e_) : "unsupported shape", __FILE__, __LINE__); } while (0)
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return moge_internal_fail(MOGE_ERR_HIP, "%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+#define LCHK(x) do { int e_ = (x); if (e_ != 0) return moge_internal_fail(e_ < 0 ? MOGE_ERR_INVALID : MOGE_ERR_HIP, "%s: launch failed (%d: %s) (%s:%d)", #x, e_, e_ > 0 ? hipGetErrorString((hipError_t)e_) : "unsupported shape", __FILE__, __LINE__); } while (0)
 #define CHK(x) do { int e_ = (x); if (e_ != 0) return e_; } while (0)
 
 static const char* HEAD_NAMES[3] = {"points_head", "normal_head", "mask_head"};
@@ -560,7 +559,7 @@ int ct3_compose_device(const float* w3, const float* wt, int ci, int co, void* w
 static int compose_ct3_f16(moge_handle* h, const std::string& name, int l, int ci, int co, hipStream_t st) {
     const int rc = ct3_compose_device(M(h, name + S(".resamplers.%d.1.weight", l)), M(h, name + S(".resamplers.%d.0.weight", l)), ci, co,
                                       Pm<f16>(h, name + S(".rs%d.wc", l)), Pm<f16>(h, name + S(".rs%d.dw", l)), st);
-    if (rc) return fail(rc < 0 ? MOGE_ERR_INVALID : MOGE_ERR_HIP, "composing the ConvTranspose2d + 3x3 weights of %s level %d failed (%d)", name.c_str(), l, rc);
+    if (rc) return moge_internal_fail(rc < 0 ? MOGE_ERR_INVALID : MOGE_ERR_HIP, "composing the ConvTranspose2d + 3x3 weights of %s level %d failed (%d)", name.c_str(), l, rc);
     return 0;
 }
 
@@ -597,7 +596,7 @@ static int compose_weights_f16(moge_handle* h, hipStream_t st) {
     } while (0);
     hipError_t e = hipStreamSynchronize(st);
     hipFree(arena);
-    if (rc) return fail(rc < 0 ? MOGE_ERR_INVALID : MOGE_ERR_HIP, "composing the level-0 linear chains failed (%d)", rc);
+    if (rc) return moge_internal_fail(rc < 0 ? MOGE_ERR_INVALID : MOGE_ERR_HIP, "composing the level-0 linear chains failed (%d)", rc);
     HIPCHK(e);
     return 0;
 }
@@ -944,7 +943,7 @@ static int res_blocks(moge_handle* h, const std::string& name, int l, int n, T* 
             // MoGe-1's deterministic slab kernels (elementwise.hip).  ReLU without a norm stays fused in the conv (input side / epilogue).
             // (the second scratch map is only touched when the first norm / activation pass writes `oth`; a hidden norm alone is applied in place)
             if ((!tmp2 && (in_norm || act != MOGE_ACT_RELU)) || (!gn && (in_norm || hid_norm)))
-                return fail(MOGE_ERR_INVALID, "res_blocks: generic blocks need a second scratch map (and the norm statistics scratch)");
+                return moge_internal_fail(MOGE_ERR_INVALID, "res_blocks: generic blocks need a second scratch map (and the norm statistics scratch)");
             const std::string r = name + S(".res_blocks.%d.%d.layers.", l, j);
             auto affine = [&](int mode, const char* key) -> const float* { return (mode == MOGE_NORM_LAYER || mode == MOGE_NORM_GROUP) ? M(h, r + key) : nullptr; };
             const T* in1 = cur;
@@ -984,12 +983,12 @@ static int res_blocks(moge_handle* h, const std::string& name, int l, int n, T* 
             }
         }
 #endif
-        if (cur != x) return fail(MOGE_ERR_INVALID, "res_blocks: internal buffer order");      // (unreachable: an unfused block only follows an even number of fused ones)
+        if (cur != x) return moge_internal_fail(MOGE_ERR_INVALID, "res_blocks: internal buffer order");      // (unreachable: an unfused block only follows an even number of fused ones)
         CHK(conv3x3<T>(h, cur, w1, b1, oth, B, Hh, Ww, C, Ch, 1, ACT_RELU, nullptr, nullptr, st));
         CHK(conv3x3<T>(h, oth, w2, b2, cur, B, Hh, Ww, Ch, C, 0, ACT_NONE, cur, nullptr, st));
     }
     if (res) *res = cur;
-    else if (cur != x) return fail(MOGE_ERR_INVALID, "res_blocks: result left in the scratch buffer");
+    else if (cur != x) return moge_internal_fail(MOGE_ERR_INVALID, "res_blocks: result left in the scratch buffer");
     return 0;
 }
 
@@ -1168,7 +1167,7 @@ static int encode(moge_handle* h, const void* image, int img_dtype, int imgH, in
                 tap_k++;
             }
     }
-    if (tap_k != c.n_taps) return fail(MOGE_ERR_INVALID, "intermediate_layers must be distinct block indices < depth");
+    if (tap_k != c.n_taps) return moge_internal_fail(MOGE_ERR_INVALID, "intermediate_layers must be distinct block indices < depth");
     if (want_feat) {   // sum_k Conv1x1_k(tap_k) == one GEMM over K = n_taps*D (modules.py:128-131)
         GemmArgs g = gemm_args();
         g.a = tapcat; g.lda = c.n_taps * D; g.w = P<T>(h, "outproj.w"); g.ldw = c.n_taps * D;
@@ -1718,31 +1717,31 @@ int moge_abi_version(void) { return MOGE_ABI_VERSION; }
 const char* moge_last_error(void) { return g_err.c_str(); }
 
 int moge_create(const moge_config* cfg, int device, moge_handle** out) {
-    if (!cfg || !out) return fail(MOGE_ERR_INVALID, "null argument");
+    if (!cfg || !out) return moge_internal_fail(MOGE_ERR_INVALID, "null argument");
     const moge_config& c = *cfg;
     if (c.embed_dim % 128 != 0 || c.embed_dim > 1024 || c.embed_dim != c.num_heads * 64)
-        return fail(MOGE_ERR_INVALID, "unsupported ViT width %d / heads %d (need head_dim 64, width %%128==0, <=1024)", c.embed_dim, c.num_heads);
-    if (c.n_taps < 1 || c.n_taps > MOGE_MAX_TAPS) return fail(MOGE_ERR_INVALID, "bad n_taps");
+        return moge_internal_fail(MOGE_ERR_INVALID, "unsupported ViT width %d / heads %d (need head_dim 64, width %%128==0, <=1024)", c.embed_dim, c.num_heads);
+    if (c.n_taps < 1 || c.n_taps > MOGE_MAX_TAPS) return moge_internal_fail(MOGE_ERR_INVALID, "bad n_taps");
     for (int l = 0; l < MOGE_LEVELS; l++)
-        if (c.dims[l] % 8 != 0 || c.dims[l] <= 0) return fail(MOGE_ERR_INVALID, "stack dims must be positive multiples of 8");
-    if (c.dims[4] > 64) return fail(MOGE_ERR_INVALID, "last level wider than 64 channels is not supported");
-    if ((c.heads & MOGE_HEAD_SCALE) && (c.scale_hidden <= 0 || c.scale_hidden % 4 != 0)) return fail(MOGE_ERR_INVALID, "bad scale_hidden");
+        if (c.dims[l] % 8 != 0 || c.dims[l] <= 0) return moge_internal_fail(MOGE_ERR_INVALID, "stack dims must be positive multiples of 8");
+    if (c.dims[4] > 64) return moge_internal_fail(MOGE_ERR_INVALID, "last level wider than 64 channels is not supported");
+    if ((c.heads & MOGE_HEAD_SCALE) && (c.scale_hidden <= 0 || c.scale_hidden % 4 != 0)) return moge_internal_fail(MOGE_ERR_INVALID, "bad scale_hidden");
     for (int l = 0; l < MOGE_LEVELS - 1; l++)
         if (c.neck_resamplers[l] < 0 || c.neck_resamplers[l] > MOGE_RS_PIXEL_SHUFFLE || c.head_resamplers[l] < 0 || c.head_resamplers[l] > MOGE_RS_PIXEL_SHUFFLE)
-            return fail(MOGE_ERR_INVALID, "bad resampler code at level %d", l);
+            return moge_internal_fail(MOGE_ERR_INVALID, "bad resampler code at level %d", l);
     for (int nk = 0; nk < 2; nk++) {
         const bool neck = nk == 1;
         const int in_n = neck ? c.neck_in_norm : c.head_in_norm, hid_n = neck ? c.neck_hidden_norm : c.head_hidden_norm;
-        if (in_n < 0 || in_n > MOGE_NORM_INSTANCE || hid_n < 0 || hid_n > MOGE_NORM_INSTANCE) return fail(MOGE_ERR_INVALID, "bad res-block norm code");
-        if (stack_act(c, neck) < 0 || stack_act(c, neck) > MOGE_ACT_ELU) return fail(MOGE_ERR_INVALID, "bad res-block activation code");
+        if (in_n < 0 || in_n > MOGE_NORM_INSTANCE || hid_n < 0 || hid_n > MOGE_NORM_INSTANCE) return moge_internal_fail(MOGE_ERR_INVALID, "bad res-block norm code");
+        if (stack_act(c, neck) < 0 || stack_act(c, neck) > MOGE_ACT_ELU) return moge_internal_fail(MOGE_ERR_INVALID, "bad res-block activation code");
         const int km = neck ? c.neck_hidden_mult : c.head_hidden_mult;
-        if (km < 0 || km > 8) return fail(MOGE_ERR_INVALID, "dim_times_res_block_hidden must be 1 ... 8 (0 = unset), got %d", km);
+        if (km < 0 || km > 8) return moge_internal_fail(MOGE_ERR_INVALID, "dim_times_res_block_hidden must be 1 ... 8 (0 = unset), got %d", km);
         for (int l = 0; l < MOGE_LEVELS; l++) {
             // the norms run on gn_partial's / in_partial's fixed slabs (as in moge_create_v1): widths 32 ... 1024, powers of two
             const int C = c.dims[l], Ch = C * stack_mult(c, neck), nb = neck ? c.neck_res_blocks[l] : c.head_res_blocks[l];
             auto pow2 = [](int v) { return v >= 32 && v <= 1024 && (v & (v - 1)) == 0; };
             if (nb > 0 && ((in_n && !pow2(C)) || (hid_n && !pow2(Ch))))
-                return fail(MOGE_ERR_INVALID, "normalised residual blocks at level %d need widths of 32 ... 1024 (powers of two), got %d (hidden %d)", l, C, Ch);
+                return moge_internal_fail(MOGE_ERR_INVALID, "normalised residual blocks at level %d need widths of 32 ... 1024 (powers of two), got %d (hidden %d)", l, C, Ch);
         }
     }
     HIPCHK(hipSetDevice(device));
@@ -1752,45 +1751,45 @@ int moge_create(const moge_config* cfg, int device, moge_handle** out) {
     memset(&h->prof_acc, 0, sizeof(h->prof_acc));
     build_tables(h);
     hipError_t e = hipMalloc(&h->d_status, sizeof(int));
-    if (e != hipSuccess) { delete h; return fail(MOGE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { delete h; return moge_internal_fail(MOGE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
     hipMemset(h->d_status, 0, sizeof(int));
     e = hipMalloc(&h->bcast_rec, 5 * sizeof(long long));                                           // status record of moge_broadcast_weights
-    if (e != hipSuccess) { hipFree(h->d_status); delete h; return fail(MOGE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { hipFree(h->d_status); delete h; return moge_internal_fail(MOGE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
     if (hipHostMalloc((void**)&h->h_status, sizeof(int), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->h_status = nullptr; }      // (optional: moge_sync falls back to a blocking copy)
     *out = h;
     return 0;
 }
 
 int moge_create_v1(const moge_v1_config* cfg, int device, moge_handle** out) {
-    if (!cfg || !out) return fail(MOGE_ERR_INVALID, "null argument");
+    if (!cfg || !out) return moge_internal_fail(MOGE_ERR_INVALID, "null argument");
     const moge_v1_config& c = *cfg;
     if (c.embed_dim % 128 != 0 || c.embed_dim > 1024 || c.embed_dim != c.num_heads * 64)
-        return fail(MOGE_ERR_INVALID, "unsupported ViT width %d / heads %d (need head_dim 64, width %%128==0, <=1024)", c.embed_dim, c.num_heads);
-    if (c.n_taps < 1 || c.n_taps > MOGE_MAX_TAPS) return fail(MOGE_ERR_INVALID, "bad n_taps");
-    if (c.n_up < 1 || c.n_up > MOGE_V1_MAX_UP) return fail(MOGE_ERR_INVALID, "bad number of upsample stages");
-    if (c.dim_proj % 32 != 0 || c.dim_proj <= 0) return fail(MOGE_ERR_INVALID, "dim_proj must be a positive multiple of 32");
+        return moge_internal_fail(MOGE_ERR_INVALID, "unsupported ViT width %d / heads %d (need head_dim 64, width %%128==0, <=1024)", c.embed_dim, c.num_heads);
+    if (c.n_taps < 1 || c.n_taps > MOGE_MAX_TAPS) return moge_internal_fail(MOGE_ERR_INVALID, "bad n_taps");
+    if (c.n_up < 1 || c.n_up > MOGE_V1_MAX_UP) return moge_internal_fail(MOGE_ERR_INVALID, "bad number of upsample stages");
+    if (c.dim_proj % 32 != 0 || c.dim_proj <= 0) return moge_internal_fail(MOGE_ERR_INVALID, "dim_proj must be a positive multiple of 32");
     for (int i = 0; i < c.n_up; i++) {
         // GroupNorm(1, C) and GroupNorm(C / 32, C) run on gn_partial's fixed slabs: 256 threads must hold a whole number of pixel rows of
         // C / 8 (fp16) and C / 4 (fp32) chunks - a power of two.  Rejected HERE, not at the first forward with a generic launch error.
         const int C = c.dim_upsample[i];
         if (C != 32 && C != 64 && C != 128 && C != 256 && C != 512)
-            return fail(MOGE_ERR_INVALID, "dim_upsample[%d] = %d: supported widths are 32, 64, 128, 256, 512 (GroupNorm(C / 32, C) slabs need a power of two)", i, C);
+            return moge_internal_fail(MOGE_ERR_INVALID, "dim_upsample[%d] = %d: supported widths are 32, 64, 128, 256, 512 (GroupNorm(C / 32, C) slabs need a power of two)", i, C);
     }
     if (c.last_conv_channels != 32 && c.last_conv_channels != 64 && c.last_conv_channels != 16)
-        return fail(MOGE_ERR_INVALID, "last_conv_channels must be 16, 32 or 64");
-    if (c.num_res_blocks < 0 || c.num_res_blocks > 8) return fail(MOGE_ERR_INVALID, "bad num_res_blocks");
-    if (c.last_res_blocks < 0 || c.last_res_blocks > 8) return fail(MOGE_ERR_INVALID, "bad last_res_blocks");
-    if (c.last_conv_size != 0 && c.last_conv_size != 1 && c.last_conv_size != 3) return fail(MOGE_ERR_INVALID, "last_conv_size must be 1 or 3");
+        return moge_internal_fail(MOGE_ERR_INVALID, "last_conv_channels must be 16, 32 or 64");
+    if (c.num_res_blocks < 0 || c.num_res_blocks > 8) return moge_internal_fail(MOGE_ERR_INVALID, "bad num_res_blocks");
+    if (c.last_res_blocks < 0 || c.last_res_blocks > 8) return moge_internal_fail(MOGE_ERR_INVALID, "bad last_res_blocks");
+    if (c.last_conv_size != 0 && c.last_conv_size != 1 && c.last_conv_size != 3) return moge_internal_fail(MOGE_ERR_INVALID, "last_conv_size must be 1 or 3");
     if (c.last_res_blocks > 0) {
         const int ch4 = c.last_conv_channels * (c.hidden_mult > 0 ? c.hidden_mult : 1);
         if (c.last_conv_channels < 32 || ch4 > 1024 || (ch4 & (ch4 - 1)))
-            return fail(MOGE_ERR_INVALID, "last residual blocks need last_conv_channels 32 or 64 and a power-of-two hidden width up to 1024 (got %d, hidden %d)", c.last_conv_channels, ch4);
+            return moge_internal_fail(MOGE_ERR_INVALID, "last residual blocks need last_conv_channels 32 or 64 and a power-of-two hidden width up to 1024 (got %d, hidden %d)", c.last_conv_channels, ch4);
     }
-    if (c.hidden_mult < 0 || c.hidden_mult > 8) return fail(MOGE_ERR_INVALID, "dim_times_res_block_hidden must be 1 ... 8 (0 = unset), got %d", c.hidden_mult);
-    if (c.res_block_norm != 0 && c.res_block_norm != MOGE_NORM_LAYER && c.res_block_norm != MOGE_NORM_GROUP) return fail(MOGE_ERR_INVALID, "res_block_norm must be group_norm or layer_norm");
+    if (c.hidden_mult < 0 || c.hidden_mult > 8) return moge_internal_fail(MOGE_ERR_INVALID, "dim_times_res_block_hidden must be 1 ... 8 (0 = unset), got %d", c.hidden_mult);
+    if (c.res_block_norm != 0 && c.res_block_norm != MOGE_NORM_LAYER && c.res_block_norm != MOGE_NORM_GROUP) return moge_internal_fail(MOGE_ERR_INVALID, "res_block_norm must be group_norm or layer_norm");
     for (int i = 0; i < c.n_up && c.num_res_blocks > 0; i++) {
         const int ch = c.dim_upsample[i] * v1_mult(c);
-        if (ch > 1024 || (ch & (ch - 1))) return fail(MOGE_ERR_INVALID, "dim_upsample[%d] x dim_times_res_block_hidden = %d: the hidden norm's slabs need a power of two up to 1024", i, ch);
+        if (ch > 1024 || (ch & (ch - 1))) return moge_internal_fail(MOGE_ERR_INVALID, "dim_upsample[%d] x dim_times_res_block_hidden = %d: the hidden norm's slabs need a power of two up to 1024", i, ch);
     }
     HIPCHK(hipSetDevice(device));
     moge_handle* h = new moge_handle();
@@ -1810,10 +1809,10 @@ int moge_create_v1(const moge_v1_config* cfg, int device, moge_handle** out) {
     memset(&h->prof_acc, 0, sizeof(h->prof_acc));
     build_tables(h);
     hipError_t e = hipMalloc(&h->d_status, sizeof(int));
-    if (e != hipSuccess) { delete h; return fail(MOGE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { delete h; return moge_internal_fail(MOGE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
     hipMemset(h->d_status, 0, sizeof(int));
     e = hipMalloc(&h->bcast_rec, 5 * sizeof(long long));                                           // status record of moge_broadcast_weights
-    if (e != hipSuccess) { hipFree(h->d_status); delete h; return fail(MOGE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { hipFree(h->d_status); delete h; return moge_internal_fail(MOGE_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
     if (hipHostMalloc((void**)&h->h_status, sizeof(int), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->h_status = nullptr; }      // (optional: moge_sync falls back to a blocking copy)
     *out = h;
     return 0;
@@ -1845,7 +1844,7 @@ void moge_destroy(moge_handle* h) {
 }
 
 int moge_alloc_master(moge_handle* h) {
-    if (!h) return fail(MOGE_ERR_INVALID, "null handle");
+    if (!h) return moge_internal_fail(MOGE_ERR_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));
     if (!h->master) {
         HIPCHK(hipMalloc(&h->master, h->master_floats * sizeof(float)));
@@ -1855,14 +1854,14 @@ int moge_alloc_master(moge_handle* h) {
 }
 
 int moge_master_blob(moge_handle* h, void** dev_ptr, size_t* bytes) {
-    if (!h || !h->master) return fail(MOGE_ERR_NOT_LOADED, "master blob not allocated");
+    if (!h || !h->master) return moge_internal_fail(MOGE_ERR_NOT_LOADED, "master blob not allocated");
     if (dev_ptr) *dev_ptr = h->master;
     if (bytes) *bytes = h->master_floats * sizeof(float);
     return 0;
 }
 
 int moge_master_ready(moge_handle* h) {
-    if (!h || !h->master) return fail(MOGE_ERR_NOT_LOADED, "master blob not allocated");
+    if (!h || !h->master) return moge_internal_fail(MOGE_ERR_NOT_LOADED, "master blob not allocated");
     HIPCHK(hipMemcpy(h->img_mean, M(h, h->mean_key), 3 * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(h->img_std, M(h, h->std_key), 3 * sizeof(float), hipMemcpyDeviceToHost));
     h->master_ready = true;
@@ -1921,15 +1920,15 @@ const RcclApi* rccl_api(std::string& why) {
 // synchronisation - per call).  The only solo returns are the two cases in which no collective can be issued at all: RCCL cannot be loaded, or the
 // communicator itself is broken (rank / size query fails) - then abort the communicator on the other ranks.
 int moge_broadcast_weights(moge_handle* h, void* nccl_comm, int root, void* stream) {
-    if (!h || !nccl_comm) return fail(MOGE_ERR_INVALID, "null argument");
+    if (!h || !nccl_comm) return moge_internal_fail(MOGE_ERR_INVALID, "null argument");
     std::string why;
     const RcclApi* apip = rccl_api(why);
-    if (!apip) return fail(MOGE_ERR_INVALID, "RCCL not available: librccl.so.1 could not be loaded (%s)", why.c_str());
+    if (!apip) return moge_internal_fail(MOGE_ERR_INVALID, "RCCL not available: librccl.so.1 could not be loaded (%s)", why.c_str());
     const RcclApi& api = *apip;
     int rank = -1, n = 0;
     int rc = api.user_rank(nccl_comm, &rank);
     if (rc == 0) rc = api.count(nccl_comm, &n);
-    if (rc != 0) return fail(MOGE_ERR_INVALID, "RCCL communicator query failed: %s", api.errstr ? api.errstr(rc) : "?");
+    if (rc != 0) return moge_internal_fail(MOGE_ERR_INVALID, "RCCL communicator query failed: %s", api.errstr ? api.errstr(rc) : "?");
     hipStream_t st = (hipStream_t)stream;
     // ---- local checks, recorded instead of returned
     int local_status = 0;
@@ -1948,23 +1947,23 @@ int moge_broadcast_weights(moge_handle* h, void* nccl_comm, int root, void* stre
         if (rc == 0) he = hipMemcpyAsync(rec, drec, sizeof(rec), hipMemcpyDeviceToHost, st);
         if (rc == 0 && he == hipSuccess) he = hipStreamSynchronize(st);
     }
-    if (rc != 0) return fail(MOGE_ERR_HIP, "ncclAllReduce (status agreement) failed: %s", api.errstr ? api.errstr(rc) : "?");
+    if (rc != 0) return moge_internal_fail(MOGE_ERR_HIP, "ncclAllReduce (status agreement) failed: %s", api.errstr ? api.errstr(rc) : "?");
     HIPCHK(he);
-    if (local_status != 0) return fail(local_status, "%s", local_msg.c_str());
-    if (rec[0] != 1) return fail(MOGE_ERR_INVALID, "another rank of the communicator is not ready to broadcast / receive weights (its own call reports why); nothing was sent");
-    if (rec[1] != -rec[2]) return fail(MOGE_ERR_INVALID, "ranks disagree on the master blob size (%lld ... %lld floats, this rank %lld): different model configs; nothing was sent",
+    if (local_status != 0) return moge_internal_fail(local_status, "%s", local_msg.c_str());
+    if (rec[0] != 1) return moge_internal_fail(MOGE_ERR_INVALID, "another rank of the communicator is not ready to broadcast / receive weights (its own call reports why); nothing was sent");
+    if (rec[1] != -rec[2]) return moge_internal_fail(MOGE_ERR_INVALID, "ranks disagree on the master blob size (%lld ... %lld floats, this rank %lld): different model configs; nothing was sent",
                                        rec[1], -rec[2], (long long)h->master_floats);
-    if (rec[3] != -rec[4]) return fail(MOGE_ERR_INVALID, "ranks disagree on the root rank (%lld ... %lld); nothing was sent", rec[3], -rec[4]);
+    if (rec[3] != -rec[4]) return moge_internal_fail(MOGE_ERR_INVALID, "ranks disagree on the root rank (%lld ... %lld); nothing was sent", rec[3], -rec[4]);
     const int NCCL_FLOAT32 = 7;                                  // ncclFloat (rccl.h ncclDataType_t)
     rc = api.bcast(h->master, h->master, h->master_floats, NCCL_FLOAT32, root, nccl_comm, st);
-    if (rc != 0) return fail(MOGE_ERR_HIP, "ncclBroadcast failed: %s", api.errstr ? api.errstr(rc) : "?");
+    if (rc != 0) return moge_internal_fail(MOGE_ERR_HIP, "ncclBroadcast failed: %s", api.errstr ? api.errstr(rc) : "?");
     HIPCHK(hipStreamSynchronize(st));
     if (rank != root) return moge_master_ready(h);               // kernel layouts are re-packed from the received master copy on next use
     return 0;
 }
 
 int moge_load_weights(moge_handle* h, const moge_tensor_desc* descs, int n, void* stream) {
-    if (!h || !descs) return fail(MOGE_ERR_INVALID, "null argument");
+    if (!h || !descs) return moge_internal_fail(MOGE_ERR_INVALID, "null argument");
     hipStream_t st = (hipStream_t)stream;
     CHK(moge_alloc_master(h));
     for (auto& kv : h->table) kv.second.loaded = false;
@@ -1972,20 +1971,20 @@ int moge_load_weights(moge_handle* h, const moge_tensor_desc* descs, int n, void
         auto it = h->table.find(descs[i].name ? descs[i].name : "");
         if (it == h->table.end()) continue;                      // strict=False
         if (it->second.numel != descs[i].numel)
-            return fail(MOGE_ERR_INVALID, "tensor %s has %lld elements, config expects %lld", descs[i].name, (long long)descs[i].numel, (long long)it->second.numel);
+            return moge_internal_fail(MOGE_ERR_INVALID, "tensor %s has %lld elements, config expects %lld", descs[i].name, (long long)descs[i].numel, (long long)it->second.numel);
         HIPCHK(hipMemcpyAsync(h->master + it->second.off, descs[i].data, (size_t)descs[i].numel * sizeof(float), hipMemcpyHostToDevice, st));
         it->second.loaded = true;
     }
     HIPCHK(hipStreamSynchronize(st));
     for (auto& kv : h->table)
-        if (!kv.second.loaded) return fail(MOGE_ERR_MISSING_KEY, "state dict is missing %s", kv.first.c_str());
+        if (!kv.second.loaded) return moge_internal_fail(MOGE_ERR_MISSING_KEY, "state dict is missing %s", kv.first.c_str());
     return moge_master_ready(h);
 }
 
 int moge_set_precision(moge_handle* h, int precision, void* stream) {
-    if (!h) return fail(MOGE_ERR_INVALID, "null handle");
-    if (precision != MOGE_FP32 && precision != MOGE_FP16 && precision != MOGE_FP16_HALF) return fail(MOGE_ERR_INVALID, "bad precision");
-    if (!h->master_ready) return fail(MOGE_ERR_NOT_LOADED, "weights not loaded");
+    if (!h) return moge_internal_fail(MOGE_ERR_INVALID, "null handle");
+    if (precision != MOGE_FP32 && precision != MOGE_FP16 && precision != MOGE_FP16_HALF) return moge_internal_fail(MOGE_ERR_INVALID, "bad precision");
+    if (!h->master_ready) return moge_internal_fail(MOGE_ERR_NOT_LOADED, "weights not loaded");
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     CHK(build_aux(h, st));
@@ -1996,23 +1995,23 @@ int moge_set_precision(moge_handle* h, int precision, void* stream) {
 }
 
 int moge_set_onnx_compatible_mode(moge_handle* h, int on) {
-    if (!h) return fail(MOGE_ERR_INVALID, "null handle");
+    if (!h) return moge_internal_fail(MOGE_ERR_INVALID, "null handle");
     h->onnx_mode = on ? 1 : 0;
     return 0;
 }
 
 int moge_workspace_bytes(moge_handle* h, int B, int H, int W, int token_rows, int token_cols, size_t* bytes) {
-    if (!h || !bytes) return fail(MOGE_ERR_INVALID, "null argument");
+    if (!h || !bytes) return moge_internal_fail(MOGE_ERR_INVALID, "null argument");
     *bytes = forward_ws_bytes(h, make_plan(h->cfg, h->prec, B, H, W, token_rows, token_cols));
     return 0;
 }
 
 static int check_call(moge_handle* h, const void* image, int B, int H, int W, int rows, int cols, int version = 2) {
-    if (!h || !image) return fail(MOGE_ERR_INVALID, "null argument");
-    if (h->version != version) return fail(MOGE_ERR_INVALID, "this handle is a MoGe-%d model: use the moge_%sforward / infer entry points", h->version, h->version == 1 ? "v1_" : "");
-    if (!h->master_ready) return fail(MOGE_ERR_NOT_LOADED, "weights not loaded");
-    if (B <= 0 || H <= 0 || W <= 0 || rows <= 0 || cols <= 0) return fail(MOGE_ERR_INVALID, "bad shape");
-    if ((long)B * rows * cols * 256 > 2000000000L) return fail(MOGE_ERR_INVALID, "batch too large for 32-bit pixel indices");
+    if (!h || !image) return moge_internal_fail(MOGE_ERR_INVALID, "null argument");
+    if (h->version != version) return moge_internal_fail(MOGE_ERR_INVALID, "this handle is a MoGe-%d model: use the moge_%sforward / infer entry points", h->version, h->version == 1 ? "v1_" : "");
+    if (!h->master_ready) return moge_internal_fail(MOGE_ERR_NOT_LOADED, "weights not loaded");
+    if (B <= 0 || H <= 0 || W <= 0 || rows <= 0 || cols <= 0) return moge_internal_fail(MOGE_ERR_INVALID, "bad shape");
+    if ((long)B * rows * cols * 256 > 2000000000L) return moge_internal_fail(MOGE_ERR_INVALID, "batch too large for 32-bit pixel indices");
     HIPCHK(hipSetDevice(h->device));
     return 0;
 }
@@ -2096,7 +2095,7 @@ static int forward_dispatch(moge_handle* h, const void* image, int img_dtype, co
 static int ingest_image(moge_handle* h, const void*& image, int& img_dtype, int B, int H, int W, hipStream_t st) {
     if (img_dtype != 2) {
         if (img_dtype != 0 && img_dtype != 1 && img_dtype != 3)
-            return fail(MOGE_ERR_INVALID, "img_dtype must be 0 (fp32 CHW), 1 (fp16 CHW), 2 (uint8 HWC) or 3 (fp32 CHW, rounded to fp16 on load)");
+            return moge_internal_fail(MOGE_ERR_INVALID, "img_dtype must be 0 (fp32 CHW), 1 (fp16 CHW), 2 (uint8 HWC) or 3 (fp32 CHW, rounded to fp16 on load)");
         return 0;
     }
     const bool half = h->prec == MOGE_FP16;
@@ -2117,7 +2116,7 @@ static int ingest_image(moge_handle* h, const void*& image, int& img_dtype, int 
 
 int moge_forward(moge_handle* h, const void* image, int img_dtype, int B, int H, int W, int rows, int cols, const moge_outputs* out, void* stream) {
     CHK(check_call(h, image, B, H, W, rows, cols));
-    if (!out) return fail(MOGE_ERR_INVALID, "null outputs");
+    if (!out) return moge_internal_fail(MOGE_ERR_INVALID, "null outputs");
     hipStream_t st = (hipStream_t)stream;
     CHK(ingest_image(h, image, img_dtype, B, H, W, st));
     Plan pl = make_plan(h->cfg, h->prec, B, H, W, rows, cols);
@@ -2146,12 +2145,12 @@ static int post_impl(moge_handle* h, const Plan& pl, const float* pts_in, const 
 int moge_infer(moge_handle* h, const void* image, int img_dtype, int B, int H, int W, int rows, int cols, const float* fov_x_deg, int flags,
                const moge_outputs* out, void* stream) {
     CHK(check_call(h, image, B, H, W, rows, cols));
-    if (!out) return fail(MOGE_ERR_INVALID, "null outputs");
+    if (!out) return moge_internal_fail(MOGE_ERR_INVALID, "null outputs");
     const moge_config& c = h->cfg;
     // every head is optional (v2.py:46-56): without a points head infer() returns the mask (no `depth > 0` term) and the masked normal (v2.py:251-298)
     const bool has_pts = (c.heads & MOGE_HEAD_POINTS) != 0;
-    if (has_pts && (!out->points || !out->depth)) return fail(MOGE_ERR_INVALID, "points and depth output buffers are required");
-    if (!has_pts && !(c.heads & (MOGE_HEAD_MASK | MOGE_HEAD_NORMAL))) return fail(MOGE_ERR_INVALID, "the model has no points, mask or normal head: infer() has nothing to return");
+    if (has_pts && (!out->points || !out->depth)) return moge_internal_fail(MOGE_ERR_INVALID, "points and depth output buffers are required");
+    if (!has_pts && !(c.heads & (MOGE_HEAD_MASK | MOGE_HEAD_NORMAL))) return moge_internal_fail(MOGE_ERR_INVALID, "the model has no points, mask or normal head: infer() has nothing to return");
     hipStream_t st = (hipStream_t)stream;
     CHK(ingest_image(h, image, img_dtype, B, H, W, st));
     Plan pl = make_plan(c, h->prec, B, H, W, rows, cols);
@@ -2165,7 +2164,7 @@ int moge_infer(moge_handle* h, const void* image, int img_dtype, int B, int H, i
 
 static int v1_check(moge_handle* h, const void* image, int B, int H, int W, int rh, int rw, void* stream) {
     CHK(check_call(h, image, B, H, W, rh / 14, rw / 14, 1));
-    if (rh < 14 || rw < 14) return fail(MOGE_ERR_INVALID, "resized image %dx%d is smaller than one 14x14 patch", rh, rw);
+    if (rh < 14 || rw < 14) return moge_internal_fail(MOGE_ERR_INVALID, "resized image %dx%d is smaller than one 14x14 patch", rh, rw);
     // lazy weight packing runs on the CALL's stream (as forward_dispatch does for v2): on the NULL stream it would race the forward of a
     // caller that uses a hipStreamNonBlocking stream and never called moge_set_precision
     if (!h->pk_ready[h->prec]) CHK(moge_set_precision(h, h->half_resid ? MOGE_FP16_HALF : h->prec, stream));
@@ -2174,7 +2173,7 @@ static int v1_check(moge_handle* h, const void* image, int B, int H, int W, int 
 
 int moge_v1_forward(moge_handle* h, const void* image, int img_dtype, int B, int H, int W, int resized_h, int resized_w, const moge_outputs* out, void* stream) {
     CHK(v1_check(h, image, B, H, W, resized_h, resized_w, stream));
-    if (!out) return fail(MOGE_ERR_INVALID, "null outputs");
+    if (!out) return moge_internal_fail(MOGE_ERR_INVALID, "null outputs");
     hipStream_t st = (hipStream_t)stream;
     CHK(ingest_image(h, image, img_dtype, B, H, W, st));
     const PlanV1 v = make_plan_v1(h, h->prec, B, H, W, resized_h, resized_w);
@@ -2186,7 +2185,7 @@ int moge_v1_forward(moge_handle* h, const void* image, int img_dtype, int B, int
 int moge_v1_infer(moge_handle* h, const void* image, int img_dtype, int B, int H, int W, int resized_h, int resized_w, const float* fov_x_deg, int flags,
                   const moge_outputs* out, void* stream) {
     CHK(v1_check(h, image, B, H, W, resized_h, resized_w, stream));
-    if (!out || !out->points || !out->depth) return fail(MOGE_ERR_INVALID, "points and depth output buffers are required");
+    if (!out || !out->points || !out->depth) return moge_internal_fail(MOGE_ERR_INVALID, "points and depth output buffers are required");
     hipStream_t st = (hipStream_t)stream;
     CHK(ingest_image(h, image, img_dtype, B, H, W, st));
     const PlanV1 v = make_plan_v1(h, h->prec, B, H, W, resized_h, resized_w);
@@ -2200,7 +2199,7 @@ int moge_v1_infer(moge_handle* h, const void* image, int img_dtype, int B, int H
 
 int moge_postprocess(moge_handle* h, const float* points_in, const float* normal_in, const float* mask_prob_in, const float* metric_scale_in,
                      int B, int H, int W, const float* fov_x_deg, int flags, const moge_outputs* out, void* stream) {
-    if (!h || !points_in || !out || !out->points || !out->depth) return fail(MOGE_ERR_INVALID, "null argument");
+    if (!h || !points_in || !out || !out->points || !out->depth) return moge_internal_fail(MOGE_ERR_INVALID, "null argument");
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     Plan pl;
@@ -2211,21 +2210,21 @@ int moge_postprocess(moge_handle* h, const float* points_in, const float* normal
 }
 
 int moge_depth_edge_mask(moge_handle* h, const float* depth, const unsigned char* mask, int B, int H, int W, float rtol, unsigned char* out, void* stream) {
-    if (!h || !depth || !out || B < 1 || H < 1 || W < 1) return fail(MOGE_ERR_INVALID, "null / empty argument");
+    if (!h || !depth || !out || B < 1 || H < 1 || W < 1) return moge_internal_fail(MOGE_ERR_INVALID, "null / empty argument");
     HIPCHK(hipSetDevice(h->device));
     LCHK(launch_depth_edge_mask(depth, mask, out, B, H, W, rtol, (hipStream_t)stream));
     return 0;
 }
 
 int moge_cast_f16(const float* src, void* dst_f16, int64_t n, void* stream) {
-    if (!src || !dst_f16 || n < 0) return fail(MOGE_ERR_INVALID, "moge_cast_f16: null argument or negative count");
+    if (!src || !dst_f16 || n < 0) return moge_internal_fail(MOGE_ERR_INVALID, "moge_cast_f16: null argument or negative count");
     if (n == 0) return 0;
     LCHK((launch_convert<float, f16>(src, dst_f16, (long)n, (hipStream_t)stream)));
     return 0;
 }
 
 int moge_sync(moge_handle* h, void* stream) {
-    if (!h) return fail(MOGE_ERR_INVALID, "null handle");
+    if (!h) return moge_internal_fail(MOGE_ERR_INVALID, "null handle");
     // ONE host wait: the status word is copied to pinned host memory on the stream, behind the work it reports on.  (Rounds 1-5 waited for the stream and then
     // ran a blocking 4-byte copy: two host round trips of ~90 us each per call - 1.4 % of a single-image infer().)
     int stv = 0;
@@ -2239,19 +2238,19 @@ int moge_sync(moge_handle* h, void* stream) {
     }
     if (stv != 0) {
         HIPCHK(hipMemset(h->d_status, 0, sizeof(int)));
-        return fail(stv, "Residuals are not finite in the initial point.");
+        return moge_internal_fail(stv, "Residuals are not finite in the initial point.");
     }
     return 0;
 }
 
 int moge_profile_enable(moge_handle* h, int on) {
-    if (!h) return fail(MOGE_ERR_INVALID, "null handle");
+    if (!h) return moge_internal_fail(MOGE_ERR_INVALID, "null handle");
     h->prof_on = on != 0;
     return 0;
 }
 
 int moge_profile_read(moge_handle* h, moge_profile* out, int reset) {
-    if (!h || !out) return fail(MOGE_ERR_INVALID, "null argument");
+    if (!h || !out) return moge_internal_fail(MOGE_ERR_INVALID, "null argument");
     for (auto& r : h->prof_pending) {
         HIPCHK(hipEventSynchronize(r.e1));
         float ms = 0.f;
@@ -2270,14 +2269,14 @@ int moge_profile_read(moge_handle* h, moge_profile* out, int reset) {
 }
 
 int moge_debug_tap(moge_handle* h, const char* name, float* dst, int64_t cap, int64_t* numel, void* stream) {
-    if (!h || !name) return fail(MOGE_ERR_INVALID, "null argument");
-    if (!h->last.valid) return fail(MOGE_ERR_INVALID, "no forward has run");
+    if (!h || !name) return moge_internal_fail(MOGE_ERR_INVALID, "null argument");
+    if (!h->last.valid) return moge_internal_fail(MOGE_ERR_INVALID, "no forward has run");
     auto it = h->last.bufs.find(name);
-    if (it == h->last.bufs.end()) return fail(MOGE_ERR_INVALID, "unknown tap %s", name);
+    if (it == h->last.bufs.end()) return moge_internal_fail(MOGE_ERR_INVALID, "unknown tap %s", name);
     const int64_t n = it->second.second.first;
     if (numel) *numel = n;
     if (!dst) return 0;
-    if (cap < n) return fail(MOGE_ERR_INVALID, "tap buffer too small");
+    if (cap < n) return moge_internal_fail(MOGE_ERR_INVALID, "tap buffer too small");
     hipStream_t st = (hipStream_t)stream;
     const char* src = h->ws + it->second.first;
     if (it->second.second.second == 0 || h->last.prec == MOGE_FP32) LCHK((launch_convert<float, float>(src, dst, n, st)));

@@ -75,7 +75,7 @@ static PanoDims pano_dims(int width, int height) {
 
 static PanoWs pano_ws(void* workspace, const PanoDims& D) {
     PanoWs w;
-    w.P = (D.M + MOGE_PANO_SPAN - 1) / MOGE_PANO_SPAN;
+    w.P = (int)blocks(D.M, MOGE_PANO_SPAN);
     w.u = (double*)workspace;
     w.v = w.u + D.M;
     w.h = w.v + D.N;
@@ -531,28 +531,15 @@ __global__ __launch_bounds__(PANO_THREADS) void pano_finish_kernel(const double*
 // ------------------------------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------------------------------
-static int pano_fail(const char* who, const char* what) {
-    char msg[240];
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    moge_internal_set_error(msg);
-    return MOGE_ERR_INVALID;
-}
-
 static int pano_check_map(int width, int height, const char* who) {         // M = 3 W H + ... row indices are int32
-    if (width < 1 || height < 1 || (int64_t)width * height > MOGE_PANO_MAX_PIXELS) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "need width >= 1, height >= 1 and width * height <= 2^29, got width = %d, height = %d", width, height);
-        return pano_fail(who, msg);
-    }
+    if (width < 1 || height < 1 || (int64_t)width * height > MOGE_PANO_MAX_PIXELS)
+        return moge_internal_fail(MOGE_ERR_INVALID, "%s: need width >= 1, height >= 1 and width * height <= 2^29, got width = %d, height = %d", who, width, height);
     return 0;
 }
 
 static int pano_check_image(int H, int W, const char* who) {
-    if (H < 1 || W < 1 || (int64_t)H * W > MOGE_PANO_MAX_PIXELS) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "need H >= 1, W >= 1 and H * W <= 2^29, got H = %d, W = %d", H, W);
-        return pano_fail(who, msg);
-    }
+    if (H < 1 || W < 1 || (int64_t)H * W > MOGE_PANO_MAX_PIXELS)
+        return moge_internal_fail(MOGE_ERR_INVALID, "%s: need H >= 1, W >= 1 and H * W <= 2^29, got H = %d, W = %d", who, H, W);
     return 0;
 }
 
@@ -565,32 +552,29 @@ static void pano_cams(const float* extrinsics, const float* intrinsics, int n, P
     }
 }
 
-static unsigned pano_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 extern "C" {
 
 int moge_pano_split(const void* image, int is_u8, int H, int W, const float* extrinsics, const float* intrinsics, int n, int resolution, void* out, void* stream) {
     if (int rc = pano_check_image(H, W, "moge_pano_split")) return rc;
-    if (n < 1 || n > MOGE_PANO_MAX_VIEWS) return pano_fail("moge_pano_split", "need 1 <= n <= MOGE_PANO_MAX_VIEWS views");
-    if (resolution < 1 || resolution > 16384) return pano_fail("moge_pano_split", "need 1 <= resolution <= 16384");
-    if (!image || !extrinsics || !intrinsics || !out) return pano_fail("moge_pano_split", "null argument");
+    if (n < 1 || n > MOGE_PANO_MAX_VIEWS) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_split: need 1 <= n <= MOGE_PANO_MAX_VIEWS views");
+    if (resolution < 1 || resolution > 16384) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_split: need 1 <= resolution <= 16384");
+    if (!image || !extrinsics || !intrinsics || !out) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_split: null argument");
     PanoCams cams;
     pano_cams(extrinsics, intrinsics, n, cams);
-    const dim3 grid(pano_blocks((int64_t)resolution * resolution, PANO_THREADS), (unsigned)n);
+    const dim3 grid(blocks((int64_t)resolution * resolution, PANO_THREADS), (unsigned)n);
     hipStream_t st = (hipStream_t)stream;
     if (is_u8) hipLaunchKernelGGL(pano_split_kernel<uint8_t>, grid, dim3(PANO_THREADS), 0, st, (const uint8_t*)image, H, W, cams, resolution, (uint8_t*)out);
     else hipLaunchKernelGGL(pano_split_kernel<float>, grid, dim3(PANO_THREADS), 0, st, (const float*)image, H, W, cams, resolution, (float*)out);
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_pano_split: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    return launched("moge_pano_split: launch failed");
 }
 
 int moge_pano_merge_workspace(int width, int height, int n, int64_t* bytes) {
-    if (!bytes) return pano_fail("moge_pano_merge_workspace", "null argument");
+    if (!bytes) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_merge_workspace: null argument");
     *bytes = 0;
     if (int rc = pano_check_map(width, height, "moge_pano_merge_workspace")) return rc;
-    if (n < 0 || n > MOGE_PANO_MAX_VIEWS) return pano_fail("moge_pano_merge_workspace", "need 0 <= n <= MOGE_PANO_MAX_VIEWS views");
+    if (n < 0 || n > MOGE_PANO_MAX_VIEWS) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_merge_workspace: need 0 <= n <= MOGE_PANO_MAX_VIEWS views");
     const PanoDims D = pano_dims(width, height);
-    const int64_t P = ((int64_t)D.M + MOGE_PANO_SPAN - 1) / MOGE_PANO_SPAN;
+    const int64_t P = blocks(D.M, MOGE_PANO_SPAN);
     *bytes = 8 * ((int64_t)D.M + 3 * (int64_t)D.N + 3 * P + MOGE_PANO_STATE_DOUBLES) + 5 * (int64_t)n * D.N;
     return 0;
 }
@@ -598,34 +582,33 @@ int moge_pano_merge_workspace(int width, int height, int n, int64_t* bytes) {
 int moge_pano_system(int width, int height, const float* distance, const uint8_t* masks, int n, int vh, int vw, const float* extrinsics, const float* intrinsics,
                      void* workspace, double* b, uint8_t* rows, uint8_t* seen, void* stream) {
     if (int rc = pano_check_map(width, height, "moge_pano_system")) return rc;
-    if (n < 1 || n > MOGE_PANO_MAX_VIEWS) return pano_fail("moge_pano_system", "need 1 <= n <= MOGE_PANO_MAX_VIEWS views");
-    if (vh < 1 || vw < 1 || (int64_t)vh * vw > MOGE_PANO_MAX_PIXELS) return pano_fail("moge_pano_system", "need view sizes >= 1 and vh * vw <= 2^29");
-    if (!distance || !masks || !extrinsics || !intrinsics || !workspace || !b || !rows || !seen) return pano_fail("moge_pano_system", "null argument");
+    if (n < 1 || n > MOGE_PANO_MAX_VIEWS) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_system: need 1 <= n <= MOGE_PANO_MAX_VIEWS views");
+    if (vh < 1 || vw < 1 || (int64_t)vh * vw > MOGE_PANO_MAX_PIXELS) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_system: need view sizes >= 1 and vh * vw <= 2^29");
+    if (!distance || !masks || !extrinsics || !intrinsics || !workspace || !b || !rows || !seen) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_system: null argument");
     const PanoDims D = pano_dims(width, height);
     PanoWs w = pano_ws(workspace, D);
     w.m = (uint8_t*)(w.logd + (int64_t)n * D.N);
     PanoCams cams;
     pano_cams(extrinsics, intrinsics, n, cams);
     hipStream_t st = (hipStream_t)stream;
-    const unsigned nb = pano_blocks(D.N, PANO_THREADS);
+    const unsigned nb = blocks(D.N, PANO_THREADS);
     hipLaunchKernelGGL(pano_warp_kernel, dim3(nb, (unsigned)n), dim3(PANO_THREADS), 0, st, distance, masks, vh, vw, cams, height, width, w.logd, w.m);
     hipLaunchKernelGGL(pano_means_kernel, dim3(nb), dim3(PANO_THREADS), 0, st, w.logd, w.m, n, D, b, rows, seen);
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_pano_system: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    return launched("moge_pano_system: launch failed");
 }
 
 int moge_pano_lsmr(int width, int height, const double* b, const uint8_t* rows, const double* x0, double atol, double btol, double conlim, int maxiter, int poll,
                    void* workspace, double* x, double* info, void* stream) {
     if (int rc = pano_check_map(width, height, "moge_pano_lsmr")) return rc;
-    if (poll < 1 || poll > 65536) return pano_fail("moge_pano_lsmr", "need 1 <= poll <= 65536 iterations per read of the stop word");
-    if (maxiter < 0) return pano_fail("moge_pano_lsmr", "maxiter must be >= 0 (0: min(selected rows, pixels))");
-    if (!(atol >= 0.0) || !(btol >= 0.0) || !(conlim >= 0.0)) return pano_fail("moge_pano_lsmr", "atol, btol and conlim must be >= 0");
-    if (!b || !rows || !workspace || !x || !info) return pano_fail("moge_pano_lsmr", "null argument");
+    if (poll < 1 || poll > 65536) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_lsmr: need 1 <= poll <= 65536 iterations per read of the stop word");
+    if (maxiter < 0) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_lsmr: maxiter must be >= 0 (0: min(selected rows, pixels))");
+    if (!(atol >= 0.0) || !(btol >= 0.0) || !(conlim >= 0.0)) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_lsmr: atol, btol and conlim must be >= 0");
+    if (!b || !rows || !workspace || !x || !info) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_lsmr: null argument");
     const PanoDims D = pano_dims(width, height);
     const PanoWs w = pano_ws(workspace, D);
     hipStream_t st = (hipStream_t)stream;
     const dim3 T(PANO_THREADS);
-    const unsigned gM = (unsigned)w.P, gN = pano_blocks(D.N, MOGE_PANO_SPAN), gN1 = pano_blocks(D.N, PANO_THREADS);
+    const unsigned gM = (unsigned)w.P, gN = blocks(D.N, MOGE_PANO_SPAN), gN1 = blocks(D.N, PANO_THREADS);
     hipLaunchKernelGGL(lsmr_init_u_kernel, dim3(gM), T, 0, st, D, b, rows, x0, w.u, w.part, w.part_b, w.part_rows);
     hipLaunchKernelGGL(lsmr_init_beta_kernel, dim3(1), T, 0, st, w.state, w.part, w.part_b, w.part_rows, w.P, D.N, maxiter, atol, btol, conlim);
     hipLaunchKernelGGL(lsmr_atu_kernel<true>, dim3(gN), T, 0, st, w.state, D, w.u, w.v, w.part);
@@ -636,7 +619,7 @@ int moge_pano_lsmr(int width, int height, const double* b, const uint8_t* rows, 
         if (hipMemcpyAsync(&hs, w.state, sizeof hs, hipMemcpyDeviceToHost, st) != hipSuccess) return false;
         return hipStreamSynchronize(st) == hipSuccess;
     };
-    if (!read_state()) { moge_internal_set_error("moge_pano_lsmr: reading the solver state failed"); return MOGE_ERR_HIP; }
+    if (!read_state()) return moge_internal_fail(MOGE_ERR_HIP, "moge_pano_lsmr: reading the solver state failed");
     int queued = 0;
     while (!hs.stop && queued < hs.maxiter) {                       // bounded by maxiter: the test kernel of iteration maxiter sets stop (istop 7)
         const int chunk = hs.maxiter - queued < poll ? hs.maxiter - queued : poll;
@@ -649,7 +632,8 @@ int moge_pano_lsmr(int width, int height, const double* b, const uint8_t* rows, 
             hipLaunchKernelGGL(lsmr_test_kernel, dim3(1), T, 0, st, w.state, w.part, (int)gN);
         }
         queued += chunk;
-        if (hipGetLastError() != hipSuccess || !read_state()) { moge_internal_set_error("moge_pano_lsmr: an iteration failed"); return MOGE_ERR_HIP; }
+        if (int rc = launched("moge_pano_lsmr: an iteration failed")) return rc;
+        if (!read_state()) return moge_internal_fail(MOGE_ERR_HIP, "moge_pano_lsmr: an iteration failed");
     }
     info[0] = hs.istop; info[1] = hs.itn; info[2] = hs.normr; info[3] = hs.normar; info[4] = hs.normA; info[5] = hs.condA; info[6] = hs.normx;
     info[7] = (double)hs.rows;
@@ -659,47 +643,42 @@ int moge_pano_lsmr(int width, int height, const double* b, const uint8_t* rows, 
 int moge_pano_resize_bilinear(const float* src, int H, int W, int out_h, int out_w, float* dst, void* stream) {
     if (int rc = pano_check_image(H, W, "moge_pano_resize_bilinear")) return rc;
     if (int rc = pano_check_image(out_h, out_w, "moge_pano_resize_bilinear")) return rc;
-    if (!src || !dst) return pano_fail("moge_pano_resize_bilinear", "null argument");
-    hipLaunchKernelGGL(pano_resize_bilinear_kernel, dim3(pano_blocks((int64_t)out_h * out_w, PANO_THREADS)), dim3(PANO_THREADS), 0, (hipStream_t)stream, src, H, W, out_h, out_w, dst);
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_pano_resize_bilinear: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    if (!src || !dst) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_resize_bilinear: null argument");
+    hipLaunchKernelGGL(pano_resize_bilinear_kernel, dim3(blocks((int64_t)out_h * out_w, PANO_THREADS)), dim3(PANO_THREADS), 0, (hipStream_t)stream, src, H, W, out_h, out_w, dst);
+    return launched("moge_pano_resize_bilinear: launch failed");
 }
 
 int moge_pano_resize_nearest(const uint8_t* src, int H, int W, int out_h, int out_w, uint8_t* dst, void* stream) {
     if (int rc = pano_check_image(H, W, "moge_pano_resize_nearest")) return rc;
     if (int rc = pano_check_image(out_h, out_w, "moge_pano_resize_nearest")) return rc;
-    if (!src || !dst) return pano_fail("moge_pano_resize_nearest", "null argument");
-    hipLaunchKernelGGL(pano_resize_nearest_kernel, dim3(pano_blocks((int64_t)out_h * out_w, PANO_THREADS)), dim3(PANO_THREADS), 0, (hipStream_t)stream, src, H, W, out_h, out_w, dst);
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_pano_resize_nearest: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    if (!src || !dst) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_resize_nearest: null argument");
+    hipLaunchKernelGGL(pano_resize_nearest_kernel, dim3(blocks((int64_t)out_h * out_w, PANO_THREADS)), dim3(PANO_THREADS), 0, (hipStream_t)stream, src, H, W, out_h, out_w, dst);
+    return launched("moge_pano_resize_nearest: launch failed");
 }
 
 int moge_pano_log(const float* src, int64_t n, double* dst, void* stream) {
-    if (n < 0 || n > MOGE_PANO_MAX_PIXELS) return pano_fail("moge_pano_log", "need 0 <= n <= 2^29");
-    if (!src || !dst) return pano_fail("moge_pano_log", "null argument");
+    if (n < 0 || n > MOGE_PANO_MAX_PIXELS) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_log: need 0 <= n <= 2^29");
+    if (!src || !dst) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_log: null argument");
     if (n == 0) return 0;
-    hipLaunchKernelGGL(pano_log_kernel, dim3(pano_blocks(n, PANO_THREADS)), dim3(PANO_THREADS), 0, (hipStream_t)stream, src, n, dst);
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_pano_log: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    hipLaunchKernelGGL(pano_log_kernel, dim3(blocks(n, PANO_THREADS)), dim3(PANO_THREADS), 0, (hipStream_t)stream, src, n, dst);
+    return launched("moge_pano_log: launch failed");
 }
 
 int moge_pano_finish(const double* x, float* distance, int H, int W, float* points, void* stream) {
     if (int rc = pano_check_image(H, W, "moge_pano_finish")) return rc;
-    if (!distance) return pano_fail("moge_pano_finish", "null argument");
-    if (!x && !points) return pano_fail("moge_pano_finish", "nothing to write (no x and no points)");
-    hipLaunchKernelGGL(pano_finish_kernel, dim3(pano_blocks((int64_t)H * W, PANO_THREADS)), dim3(PANO_THREADS), 0, (hipStream_t)stream, x, distance, H, W, points);
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_pano_finish: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    if (!distance) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_finish: null argument");
+    if (!x && !points) return moge_internal_fail(MOGE_ERR_INVALID, "moge_pano_finish: nothing to write (no x and no points)");
+    hipLaunchKernelGGL(pano_finish_kernel, dim3(blocks((int64_t)H * W, PANO_THREADS)), dim3(PANO_THREADS), 0, (hipStream_t)stream, x, distance, H, W, points);
+    return launched("moge_pano_finish: launch failed");
 }
 
 int moge_test_pano_apply(int width, int height, const uint8_t* rows, int transpose, const double* in, double* out, void* stream) {
     if (int rc = pano_check_map(width, height, "moge_test_pano_apply")) return rc;
-    if (transpose != 0 && transpose != 1) return pano_fail("moge_test_pano_apply", "transpose must be 0 or 1");
-    if (!rows || !in || !out) return pano_fail("moge_test_pano_apply", "null argument");
+    if (transpose != 0 && transpose != 1) return moge_internal_fail(MOGE_ERR_INVALID, "moge_test_pano_apply: transpose must be 0 or 1");
+    if (!rows || !in || !out) return moge_internal_fail(MOGE_ERR_INVALID, "moge_test_pano_apply: null argument");
     const PanoDims D = pano_dims(width, height);
-    hipLaunchKernelGGL(pano_apply_kernel, dim3(pano_blocks(transpose ? D.N : D.M, PANO_THREADS)), dim3(PANO_THREADS), 0, (hipStream_t)stream, D, rows, transpose, in, out);
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_test_pano_apply: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    hipLaunchKernelGGL(pano_apply_kernel, dim3(blocks(transpose ? D.N : D.M, PANO_THREADS)), dim3(PANO_THREADS), 0, (hipStream_t)stream, D, rows, transpose, in, out);
+    return launched("moge_test_pano_apply: launch failed");
 }
 
 }   // extern "C"

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_iter_kernel(RefineArgs 
 // ------------------------------------------------------------------------------------------------------------------------
 template <int K, bool MASKED>
 static int refine_run(RefineArgs g, int B, int iterations, float* xa, float* xb, hipStream_t st) {
-    const dim3 grid((unsigned)((g.W + REFINE_TILE - 1) / REFINE_TILE), (unsigned)((g.H + REFINE_TILE - 1) / REFINE_TILE), (unsigned)B);
+    const dim3 grid(blocks(g.W, REFINE_TILE), blocks(g.H, REFINE_TILE), (unsigned)B);
     hipLaunchKernelGGL((refine_prep_kernel<K, MASKED>), grid, dim3(REFINE_THREADS), 0, st, g, iterations == 0 ? 1 : 0);
     const float* src = g.x0;                        // x0 -> A -> B -> A ...: a plane is never updated in place; the last iteration writes `out`
     float* dst = xa;
@@ -196,24 +196,19 @@ static int refine_run(RefineArgs g, int B, int iterations, float* xa, float* xb,
         src = dst;
         dst = dst == xa ? xb : xa;
     }
-    if (hipGetLastError() != hipSuccess) { moge_internal_set_error("moge_refine_depth: launch failed"); return MOGE_ERR_HIP; }
-    return 0;
+    return launched("moge_refine_depth: launch failed");
 }
 
 static int refine_check(int B, int H, int W, const char* who) {
-    if (B < 0 || B > 65535 || H < 1 || W < 1 || H > 65535 * REFINE_TILE || (int64_t)H * W > INT_MAX) {      // grid.y, grid.z <= 65535
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: need 0 <= B <= 65535, 1 <= H <= %d and H * W < 2^31, got B = %d, H = %d, W = %d", who, 65535 * REFINE_TILE, B, H, W);
-        moge_internal_set_error(msg);
-        return MOGE_ERR_INVALID;
-    }
+    if (B < 0 || B > 65535 || H < 1 || W < 1 || H > 65535 * REFINE_TILE || (int64_t)H * W > INT_MAX)      // grid.y, grid.z <= 65535
+        return moge_internal_fail(MOGE_ERR_INVALID, "%s: need 0 <= B <= 65535, 1 <= H <= %d and H * W < 2^31, got B = %d, H = %d, W = %d", who, 65535 * REFINE_TILE, B, H, W);
     return 0;
 }
 
 extern "C" {
 
 int moge_refine_depth_workspace(int B, int H, int W, int64_t* bytes) {
-    if (!bytes) { moge_internal_set_error("moge_refine_depth_workspace: null argument"); return MOGE_ERR_INVALID; }
+    if (!bytes) return moge_internal_fail(MOGE_ERR_INVALID, "moge_refine_depth_workspace: null argument");
     *bytes = 0;
     if (int rc = refine_check(B, H, W, "moge_refine_depth_workspace")) return rc;
     *bytes = 4 * (int64_t)B * H * W * (int64_t)sizeof(float);           // x0, lap, two iterates
@@ -222,11 +217,11 @@ int moge_refine_depth_workspace(int B, int H, int W, int64_t* bytes) {
 
 int moge_refine_depth(const float* depth, const float* normal, const float* intrinsics, const uint8_t* mask, int B, int H, int W, int kernel_size,
                       int iterations, float damp, float eps, void* workspace, float* out, void* stream) {
-    if (!depth || !normal || !intrinsics || !workspace || !out) { moge_internal_set_error("moge_refine_depth: null argument"); return MOGE_ERR_INVALID; }
+    if (!depth || !normal || !intrinsics || !workspace || !out) return moge_internal_fail(MOGE_ERR_INVALID, "moge_refine_depth: null argument");
     if (int rc = refine_check(B, H, W, "moge_refine_depth")) return rc;
-    if (kernel_size != 3 && kernel_size != 5 && kernel_size != 7) { moge_internal_set_error("moge_refine_depth: kernel_size must be 3, 5 or 7"); return MOGE_ERR_INVALID; }
-    if (H < kernel_size || W < kernel_size) { moge_internal_set_error("moge_refine_depth: the map is smaller than the window"); return MOGE_ERR_INVALID; }
-    if (iterations < 0) { moge_internal_set_error("moge_refine_depth: iterations < 0"); return MOGE_ERR_INVALID; }
+    if (kernel_size != 3 && kernel_size != 5 && kernel_size != 7) return moge_internal_fail(MOGE_ERR_INVALID, "moge_refine_depth: kernel_size must be 3, 5 or 7");
+    if (H < kernel_size || W < kernel_size) return moge_internal_fail(MOGE_ERR_INVALID, "moge_refine_depth: the map is smaller than the window");
+    if (iterations < 0) return moge_internal_fail(MOGE_ERR_INVALID, "moge_refine_depth: iterations < 0");
     if (B == 0) return 0;
     const size_t n = (size_t)B * H * W;
     float* ws = (float*)workspace;

@@ -29,6 +29,7 @@ import torch
 from PIL import Image, PngImagePlugin
 
 from . import _lib as L
+from ._lib import ptr
 from .io import uv_map
 
 QUANTILE = 0.01                       # dataloader.py:167
@@ -230,60 +231,49 @@ def warp_geometry(raw_height: int, raw_width: int, intrinsics: np.ndarray, width
 # ------------------------------------------------------------------------------------------------------------------------------------------
 # GPU warp
 # ------------------------------------------------------------------------------------------------------------------------------------------
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _host_f32(a: np.ndarray):
     buf = np.ascontiguousarray(a, dtype=np.float32).ravel()
     return buf, C.c_void_p(buf.ctypes.data)
 
 
-def _need_cuda(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("moge_amd.evaluation works on GPU tensors only (no CPU path)")
-
-
 def lanczos_resize(image: torch.Tensor, height: int, width: int) -> torch.Tensor:
     """PIL Image.resize((width, height), LANCZOS) of an (H, W, 3) uint8 CUDA tensor, bit-exact to Pillow."""
-    _need_cuda(image)
+    dev = L.device_of("evaluation", image)
     image = image.contiguous()
     H, W = image.shape[:2]
     tmp_bytes, n_coeff = C.c_int64(), C.c_int64()
     L.check(L.lib.moge_eval_lanczos_workspace(H, W, height, width, C.byref(tmp_bytes), C.byref(n_coeff)))
-    tmp = torch.empty(tmp_bytes.value, dtype=torch.uint8, device=image.device)
-    coeffs = torch.empty(n_coeff.value, dtype=torch.int32, device=image.device)
-    out = torch.empty((height, width, 3), dtype=torch.uint8, device=image.device)
-    L.check(L.lib.moge_eval_lanczos(_p(image), H, W, height, width, _p(tmp), _p(coeffs), _p(out), _stream()))
+    tmp = torch.empty(tmp_bytes.value, dtype=torch.uint8, device=dev)
+    coeffs = torch.empty(n_coeff.value, dtype=torch.int32, device=dev)
+    out = torch.empty((height, width, 3), dtype=torch.uint8, device=dev)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_eval_lanczos(ptr(image), H, W, height, width, ptr(tmp), ptr(coeffs), ptr(out), st))
     return out
 
 
 def masked_nearest_resize_distance(depth: torch.Tensor, mask: torch.Tensor, size: Tuple[int, int], intrinsics: np.ndarray):
     """dataloader.py:147-148 -> (depth, mask (uint8), distance) of size (h, w)."""
-    _need_cuda(depth, mask)
+    dev = L.device_of("evaluation", depth, mask)
     H, W = depth.shape
     h, w = size
-    out_depth = torch.empty((h, w), dtype=torch.float32, device=depth.device)
-    out_mask = torch.empty((h, w), dtype=torch.uint8, device=depth.device)
-    distance = torch.empty((h, w), dtype=torch.float32, device=depth.device)
+    out_depth = torch.empty((h, w), dtype=torch.float32, device=dev)
+    out_mask = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    distance = torch.empty((h, w), dtype=torch.float32, device=dev)
     K = intrinsics
-    L.check(L.lib.moge_eval_masked_nearest(_p(depth.float().contiguous()), _p(mask.to(torch.uint8).contiguous()), H, W, h, w, float(K[0, 0]), float(K[1, 1]),
-                                           float(K[0, 2]), float(K[1, 2]), _p(out_depth), _p(out_mask), _p(distance), _stream()))
+    with L.on(dev) as st:
+        L.check(L.lib.moge_eval_masked_nearest(ptr(depth.float().contiguous()), ptr(mask.to(torch.uint8).contiguous()), H, W, h, w, float(K[0, 0]), float(K[1, 1]),
+                                               float(K[0, 2]), float(K[1, 2]), ptr(out_depth), ptr(out_mask), ptr(distance), st))
     return out_depth, out_mask, distance
 
 
 def resize_nearest(seg: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
     """cv2.resize(seg, (w, h), INTER_NEAREST) of a uint8 / uint16 (H, W) CUDA label map."""
-    _need_cuda(seg)
+    dev = L.device_of("evaluation", seg)
     H, W = seg.shape
     h, w = size
-    out = torch.empty((h, w), dtype=seg.dtype, device=seg.device)
-    L.check(L.lib.moge_eval_resize_nearest(_p(seg.contiguous()), seg.element_size(), H, W, h, w, _p(out), _stream()))
+    out = torch.empty((h, w), dtype=seg.dtype, device=dev)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_eval_resize_nearest(ptr(seg.contiguous()), seg.element_size(), H, W, h, w, ptr(out), st))
     return out
 
 
@@ -293,8 +283,7 @@ def warp_sample(image: torch.Tensor, depth: torch.Tensor, depth_mask: torch.Tens
     """dataloader.py:108-180 on the GPU for one sample whose raw maps are already CUDA tensors (image (H, W, 3) uint8, depth (H, W) float32
     with invalid pixels already replaced, depth_mask (H, W) bool, segmentation (H, W) uint8 / uint16 or None).  Returns the target maps
     (CUDA), the host geometry and the device-side `count` of the final mask (0 means the empty-mask fallback ran).  No host synchronisation."""
-    _need_cuda(image, depth, depth_mask, segmentation)
-    dev = image.device
+    dev = L.device_of("evaluation", image, depth, depth_mask, segmentation)
     geo = geometry or warp_geometry(image.shape[0], image.shape[1], intrinsics, width, height)
     h, w = geo["rescaled_size"]
     rescaled = lanczos_resize(image, h, w)
@@ -309,16 +298,16 @@ def warp_sample(image: torch.Tensor, depth: torch.Tensor, depth_mask: torch.Tens
     tgt_seg = torch.empty((height, width), dtype=torch.int32, device=dev) if r_seg is not None else None
     hist = torch.empty(SEG_BINS, dtype=torch.int32, device=dev) if r_seg is not None else None
     mats, mats_p = _host_f32(np.concatenate([np.asarray(geo["transform"], np.float32).ravel(), np.asarray(geo["tgt_intrinsics_inv"], np.float32).ravel()]))
-    L.check(L.lib.moge_eval_remap(_p(rescaled), _p(distance), _p(r_mask), _p(r_seg), 0 if r_seg is None else r_seg.element_size(), h, w, height, width,
-                                  mats_p, _p(image_u8), _p(image_f), _p(tgt_depth), _p(tgt_mask), _p(tgt_seg), _p(hist), _stream()))
-
     workspace = torch.empty(QUANTILE_WORKSPACE, dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    L.check(L.lib.moge_eval_quantile_cut(_p(tgt_depth), _p(tgt_mask), n, QUANTILE, float(drop_max_depth), float(depth_unit or 0.0),
-                                         int(depth_unit is not None), _p(workspace), _p(count), _stream()))
     points = torch.empty((height, width, 3), dtype=torch.float32, device=dev)
     kinv, kinv_p = _host_f32(geo["tgt_intrinsics_inv"])
-    L.check(L.lib.moge_eval_unproject(_p(tgt_depth), _p(tgt_mask), height, width, kinv_p, _p(count), _p(points), _stream()))
+    with L.on(dev) as st:
+        L.check(L.lib.moge_eval_remap(ptr(rescaled), ptr(distance), ptr(r_mask), ptr(r_seg), 0 if r_seg is None else r_seg.element_size(), h, w, height, width,
+                                      mats_p, ptr(image_u8), ptr(image_f), ptr(tgt_depth), ptr(tgt_mask), ptr(tgt_seg), ptr(hist), st))
+        L.check(L.lib.moge_eval_quantile_cut(ptr(tgt_depth), ptr(tgt_mask), n, QUANTILE, float(drop_max_depth), float(depth_unit or 0.0),
+                                             int(depth_unit is not None), ptr(workspace), ptr(count), st))
+        L.check(L.lib.moge_eval_unproject(ptr(tgt_depth), ptr(tgt_mask), height, width, kinv_p, ptr(count), ptr(points), st))
     del mats, kinv          # read during the calls (host pointers)
     return {"geometry": geo, "rescaled_image": rescaled, "image_u8": image_u8, "image": image_f, "depth": tgt_depth, "depth_mask": tgt_mask.bool(),
             "points": points, "segmentation_mask": tgt_seg, "segmentation_hist": hist, "count": count,

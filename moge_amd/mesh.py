@@ -18,6 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from ._lib import ptr
 
 BLOCK_PX = L.MESH_BLOCK_PX          # include/moge_hip.h MOGE_MESH_BLOCK_PX: consecutive pixels one workgroup of the scan ranks
 SCAN_SPAN = L.MESH_SCAN_SPAN        # MOGE_MESH_SCAN_SPAN: workgroup totals one workgroup of the second scan level covers (the tests place shapes on both)
@@ -40,11 +41,7 @@ def _prepare(maps: Sequence, mask: Optional[torch.Tensor], batched: Optional[boo
     tensors = [m for m in maps if not isinstance(m, str)] + ([mask] if mask is not None else [])
     if not tensors:
         raise ValueError("need at least one map or a mask")
-    for t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"expected torch tensors, got {type(t).__name__}")
-        if not t.is_cuda:
-            raise RuntimeError("moge_amd.mesh works on GPU tensors only (no CPU path: moge_amd.io is the host form)")
+    dev = L.device_of("mesh", *tensors, host="moge_amd.io", tensors_only=True)
     if len(maps) > MAX_MAPS:
         raise ValueError(f"at most {MAX_MAPS} maps per call, got {len(maps)}")
     if batched is None:                                 # a mask says it; without one a 3-D map is (H, W, C), as in the host function
@@ -79,7 +76,7 @@ def _prepare(maps: Sequence, mask: Optional[torch.Tensor], batched: Optional[boo
         if mask.dtype not in (torch.bool, torch.uint8):
             raise ValueError(f"mask must be bool (or uint8), got {mask.dtype}")
         mk = mask.reshape(B, H, W).contiguous().view(torch.uint8)
-    return batched, B, H, W, ref.device, specs, mk
+    return batched, B, H, W, dev, specs, mk
 
 
 def _compact(maps: Sequence, mask, tri: Optional[bool], points: bool, transforms: Optional[Sequence] = None, batched: Optional[bool] = None):
@@ -89,13 +86,11 @@ def _compact(maps: Sequence, mask, tri: Optional[bool], points: bool, transforms
     faces_w = 3 if tri else 4
     if B == 0:
         return batched, []
-    with torch.cuda.device(dev):
-        ws = torch.empty(workspace_bytes(B, H, W), device=dev, dtype=torch.uint8)
-        counts = torch.empty((B, 2), device=dev, dtype=torch.int32)
-        offsets = torch.empty((B, 2), device=dev, dtype=torch.int64)
-        stream = L.stream_ptr(dev)
-        L.check(L.lib.moge_image_mesh_count(mk.data_ptr() if mk is not None else None, B, H, W, 1 if points else 0, ws.data_ptr(), counts.data_ptr(),
-                                            offsets.data_ptr(), stream))
+    ws = torch.empty(workspace_bytes(B, H, W), device=dev, dtype=torch.uint8)
+    counts = torch.empty((B, 2), device=dev, dtype=torch.int32)
+    offsets = torch.empty((B, 2), device=dev, dtype=torch.int64)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_image_mesh_count(ptr(mk), B, H, W, 1 if points else 0, ptr(ws), ptr(counts), ptr(offsets), st))
         cnt = counts.cpu().tolist()                     # the one host read-back: the outputs' sizes
         V, Q = sum(c[0] for c in cnt), sum(c[1] for c in cnt)
         outs = [torch.empty((V, ch), device=dev, dtype=torch.float32) for _, ch, _ in specs]
@@ -103,13 +98,12 @@ def _compact(maps: Sequence, mask, tri: Optional[bool], points: bool, transforms
         if V > 0 and (specs or tri is not None):        # an empty result launches nothing
             arr = (L.MeshMap * max(1, len(specs)))()
             for a, (t, ch, code), o, (scale, offset) in zip(arr, specs, outs, transforms):
-                a.data, a.out, a.channels, a.dtype = (t.data_ptr() if t is not None else None), o.data_ptr(), ch, code
+                a.data, a.out, a.channels, a.dtype = ptr(t), ptr(o), ch, code
                 a.has_scale, a.has_offset = int(scale is not None), int(offset is not None)
                 for k in range(ch):
                     a.scale[k] = scale[k] if scale is not None else 1.0
                     a.offset[k] = offset[k] if offset is not None else 0.0
-            L.check(L.lib.moge_image_mesh_fill(B, H, W, ws.data_ptr(), arr, len(specs), L.MESH_NO_FACES if tri is None else int(bool(tri)),
-                                               faces.data_ptr() if faces is not None else None, offsets.data_ptr(), stream))
+            L.check(L.lib.moge_image_mesh_fill(B, H, W, ptr(ws), arr, len(specs), L.MESH_NO_FACES if tri is None else int(bool(tri)), ptr(faces), ptr(offsets), st))
     res, v0, q0 = [], 0, 0
     per = 2 if tri else 1
     for v, q in cnt:

@@ -14,7 +14,6 @@ One image per call; every tensor lives on the GPU (`cuda`) - there is no CPU pat
     DESIGN.md section 10: unpinned, like the other utils3d stand-ins)."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, Optional, Tuple
 
@@ -23,6 +22,7 @@ import torch
 
 from . import _lib as L
 from . import alignment as A
+from ._lib import ptr
 
 PARTIALS = 256                      # MOGE_METRICS_PARTIALS (include/moge_hip.h)
 MAX_SEGMENTS = 512                  # MOGE_METRICS_MAX_SEGMENTS
@@ -31,20 +31,6 @@ BOUNDARY_T = torch.linspace(0.05, 0.25, 10).tolist()      # metrics.py:80 (weigh
 
 # error-pass transform modes (moge_metrics_error)
 _SCALE, _AFFINE, _SHIFT, _DISP = 0, 1, 2, 3
-
-
-def _need_cuda(*ts):
-    for t in ts:
-        if t is not None and isinstance(t, torch.Tensor) and not t.is_cuda:
-            raise RuntimeError("moge_amd.metrics works on GPU tensors only (no CPU path)")
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _h2d(values, dtype, device) -> torch.Tensor:
@@ -66,12 +52,13 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
 def masked_nearest_resize(*image: torch.Tensor, mask: torch.Tensor, size: Tuple[int, int], return_index: bool = False):
     """utils3d.pt.masked_nearest_resize for one (H, W) mask: -> (*resized images, lr_mask (h, w) bool[, (rows, cols) int64 (h, w)]) with
     `image[rows, cols]` the nearest valid pixel of each low-resolution cell (convention: csrc/metrics.hip, lr_sample_kernel)."""
-    _need_cuda(mask, *image)
+    dev = L.device_of("metrics", mask, *image)
     H, W = mask.shape[-2:]
     h, w = size
-    lr_mask = torch.empty((h, w), device=mask.device, dtype=torch.uint8)
-    index = torch.empty((2, h, w), device=mask.device, dtype=torch.int32)
-    L.check(L.lib.moge_metrics_lr_sample(_p(_u8(mask)), H, W, h, w, _p(lr_mask), _p(index), _stream()))
+    lr_mask = torch.empty((h, w), device=dev, dtype=torch.uint8)
+    index = torch.empty((2, h, w), device=dev, dtype=torch.int32)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_metrics_lr_sample(ptr(_u8(mask)), H, W, h, w, ptr(lr_mask), ptr(index), st))
     rows, cols = index[0].long(), index[1].long()
     out = tuple(im[..., rows, cols, :] if im.dim() == 3 else im[..., rows, cols] for im in image) + (lr_mask.bool(),)
     if return_index:
@@ -119,30 +106,35 @@ def _params(mode: int, scale=None, shift=None, clamp: float = 0.0, device=None) 
 
 def error_pass(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
     """pred / gt (..., d) or (...) with mask (...); params (K, 6) -> (K, 3) float64 on the device: (sum rel, delta1 count, mask count)."""
+    dev = L.device_of("metrics", pred, gt, mask, params)
     dim = 3 if pred.dim() == mask.dim() + 1 else 1
     pred, gt, params = _f32(pred), _f32(gt), _f32(params)
     K = params.shape[0]
-    part = torch.empty(PARTIALS * K * 3, device=pred.device, dtype=torch.float64)
-    out = torch.empty((K, 3), device=pred.device, dtype=torch.float64)
-    L.check(L.lib.moge_metrics_error(_p(pred), _p(gt), _p(_u8(mask)), mask.numel(), dim, _p(params), K, _p(part), _p(out), _stream()))
+    part = torch.empty(PARTIALS * K * 3, device=dev, dtype=torch.float64)
+    out = torch.empty((K, 3), device=dev, dtype=torch.float64)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_metrics_error(ptr(pred), ptr(gt), ptr(_u8(mask)), mask.numel(), dim, ptr(params), K, ptr(part), ptr(out), st))
     return out
 
 
 def masked_max(x: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    dev = L.device_of("metrics", x, mask)
     x = _f32(x)
-    part = torch.empty(PARTIALS, device=x.device, dtype=torch.float32)
-    out = torch.empty(1, device=x.device, dtype=torch.float32)
-    L.check(L.lib.moge_metrics_masked_max(_p(x), _p(_u8(mask)), mask.numel(), _p(part), _p(out), _stream()))
+    part = torch.empty(PARTIALS, device=dev, dtype=torch.float32)
+    out = torch.empty(1, device=dev, dtype=torch.float32)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_metrics_masked_max(ptr(x), ptr(_u8(mask)), mask.numel(), ptr(part), ptr(out), st))
     return out[0]
 
 
 def boundary_counts(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """(H, W) maps -> (3, 10, 3) int64 on the device: per radius 1..3 and threshold, (TP, gt-label, pred-label) over the valid pairs."""
-    _need_cuda(pred, gt, mask)
+    dev = L.device_of("metrics", pred, gt, mask)
     H, W = mask.shape[-2:]
     pred, gt = _f32(pred), _f32(gt)
-    counts = torch.empty((3, 10, 3), device=pred.device, dtype=torch.int64)
-    L.check(L.lib.moge_metrics_boundary(_p(pred), _p(gt), _p(_u8(mask)), H, W, _p(counts), _stream()))
+    counts = torch.empty((3, 10, 3), device=dev, dtype=torch.int64)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_metrics_boundary(ptr(pred), ptr(gt), ptr(_u8(mask)), H, W, ptr(counts), st))
     return counts
 
 
@@ -166,7 +158,7 @@ def _weighted(f1s):
 # the reference's metric functions (metrics.py:25-92), on CUDA tensors
 # ------------------------------------------------------------------------------------------------------------------------------------------
 def _single(pred, gt, eps):
-    _need_cuda(pred, gt)
+    L.device_of("metrics", pred, gt)
     if eps != 1e-6:
         raise NotImplementedError("the kernels use the reference's eps = 1e-6")
     mask = torch.ones(gt.shape[:-1] if pred.dim() > 1 and pred.shape[-1] == 3 and pred.dim() == gt.dim() and gt.dim() >= 2 else gt.shape,
@@ -192,7 +184,7 @@ def delta1_point(pred: torch.Tensor, gt: torch.Tensor, eps: float = 1e-6):
 
 
 def _local(pred, gt, diameter):
-    _need_cuda(pred, gt, diameter)
+    L.device_of("metrics", pred, gt, diameter)
     n = pred.shape[0]
     seg = torch.zeros(n, device=pred.device, dtype=torch.int32)
     labels = torch.zeros(1, device=pred.device, dtype=torch.int32)
@@ -223,10 +215,12 @@ def boundary_f1(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, radius
 # ------------------------------------------------------------------------------------------------------------------------------------------
 def _segment_error(seg, mask, pred, gt, labels, U, row, kept, scale, shift, diameter):
     E = kept.numel()
-    part = torch.empty(PARTIALS * E * 3, device=pred.device, dtype=torch.float64)
-    out = torch.empty((E, 3), device=pred.device, dtype=torch.float64)
-    L.check(L.lib.moge_metrics_segment_error(_p(seg), _p(_u8(mask)), _p(pred), _p(gt), mask.numel(), _p(labels), U, _p(row), _p(kept), E,
-                                             _p(_f32(scale)), _p(_f32(shift)), _p(diameter), _p(part), _p(out), _stream()))
+    dev = pred.device
+    part = torch.empty(PARTIALS * E * 3, device=dev, dtype=torch.float64)
+    out = torch.empty((E, 3), device=dev, dtype=torch.float64)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_metrics_segment_error(ptr(seg), ptr(_u8(mask)), ptr(pred), ptr(gt), mask.numel(), ptr(labels), U, ptr(row), ptr(kept), E,
+                                                 ptr(_f32(scale)), ptr(_f32(shift)), ptr(diameter), ptr(part), ptr(out), st))
     return out
 
 
@@ -234,7 +228,7 @@ def local_points(pred_points, gt_points, mask, segmentation_mask, segmentation_l
     """metrics.py:283-311 -> key_average of the kept segments' {'rel', 'delta1'}.  Two host synchronisations (the low-resolution counts, the
     results) plus those of the one batched solve, whatever the number of segments.  `details` (optional dict) receives per-entry diameter /
     scale / shift / rel / delta1 of the kept segments, in segmentation_labels order."""
-    dev = pred_points.device
+    dev = L.device_of("metrics", pred_points, gt_points, mask, segmentation_mask, lr_mask, *lr_index)
     H, W = mask.shape[-2:]
     h, w = lr_mask.shape
     entries = list(segmentation_labels.values())
@@ -253,8 +247,9 @@ def local_points(pred_points, gt_points, mask, segmentation_mask, segmentation_l
     lr_count = torch.empty(U, device=dev, dtype=torch.int32)
     diameter = torch.empty(U, device=dev, dtype=torch.float32)
     m8 = _u8(mask)
-    L.check(L.lib.moge_metrics_segment_stats(_p(seg), _p(m8), _p(gt_points), H, W, _p(lr_u8), _p(index), h, w, _p(labels), U, _p(bbox),
-                                             _p(lr_count), _p(diameter), _stream()))
+    with L.on(dev) as st:
+        L.check(L.lib.moge_metrics_segment_stats(ptr(seg), ptr(m8), ptr(gt_points), H, W, ptr(lr_u8), ptr(index), h, w, ptr(labels), U, ptr(bbox),
+                                                 ptr(lr_count), ptr(diameter), st))
     counts = lr_count.cpu().tolist()                                                            # host sync 1
     kept_u = [u for u in range(U) if counts[u] >= 10]                                           # :299-300
     if not kept_u:
@@ -268,8 +263,9 @@ def local_points(pred_points, gt_points, mask, segmentation_mask, segmentation_l
     src = torch.empty((E, n_max, 3), device=dev)
     tgt = torch.empty_like(src)
     wt = torch.empty((E, n_max), device=dev)
-    L.check(L.lib.moge_metrics_segment_pack(_p(seg), W, _p(lr_u8), _p(index), h, w, _p(labels), U, _p(kept), E, n_max, _p(pred_points), _p(gt_points),
-                                            _p(diameter), _p(src), _p(tgt), _p(wt), _stream()))
+    with L.on(dev) as st:
+        L.check(L.lib.moge_metrics_segment_pack(ptr(seg), W, ptr(lr_u8), ptr(index), h, w, ptr(labels), U, ptr(kept), E, n_max, ptr(pred_points), ptr(gt_points),
+                                                ptr(diameter), ptr(src), ptr(tgt), ptr(wt), st))
     scale, shift = A.align_points_scale_xyz_shift(src, tgt, wt)                                  # all segments, one batched solve
     res = _segment_error(seg, mask, pred_points, gt_points, labels, U, row, kept, scale, shift, diameter)
     res = res.cpu().numpy()                                                                     # host sync 2
@@ -291,13 +287,12 @@ def local_points(pred_points, gt_points, mask, segmentation_mask, segmentation_l
 def compute_metrics(pred: Dict[str, torch.Tensor], gt: Dict[str, torch.Tensor], vis: bool = False, stages: Optional[dict] = None):
     """metrics.py:95-341: same keys, fall-backs, gates, nested output keys in the same order (Python floats) and the same `misc` with vis=True.
     `stages` (optional dict) receives CUDA events around the stages for tools/bench_metrics.py."""
-    _need_cuda(*pred.values(), gt['depth_mask'], gt['depth'], gt.get('points'))
+    dev = L.device_of("metrics", *(v for v in pred.values() if isinstance(v, torch.Tensor)), gt['depth_mask'], gt['depth'], gt.get('points'))
     ev = _Stages(stages)
     metrics, misc = {}, {}
     mask = gt['depth_mask'].bool()
     gt_depth = _f32(gt['depth'])
     gt_points = gt.get('points')
-    dev = mask.device
     H, W = mask.shape[-2:]
 
     ev.mark('lr_sample')

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._lib import ptr
 from .panorama import get_panorama_cameras, intrinsics_to_fov_x_deg
 
 MAX_VIEWS = L.PANO_MAX_VIEWS        # include/moge_hip.h MOGE_PANO_MAX_VIEWS
@@ -70,12 +71,8 @@ def workspace_bytes(width: int, height: int, n: int) -> int:
     return nb.value
 
 
-def _require_cuda(*tensors):
-    for t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"expected torch tensors, got {type(t).__name__}")
-        if not t.is_cuda:
-            raise RuntimeError("moge_amd.panorama_gpu works on GPU tensors only (no CPU path: moge_amd.panorama is the host form)")
+def _device(*tensors) -> torch.device:
+    return L.device_of("panorama_gpu", *tensors, host="moge_amd.panorama", tensors_only=True)
 
 
 def _cameras(extrinsics, intrinsics, n: Optional[int] = None):
@@ -111,7 +108,7 @@ def _check_map(width: int, height: int):
 def split_panorama_image(image: torch.Tensor, extrinsics, intrinsics, resolution: int) -> torch.Tensor:
     """`moge_amd.panorama.split_panorama_image` on the device: image (H, W, 3) uint8 or float32 -> views (n, resolution, resolution, 3) of the
     image's dtype (uint8 views are ready for `model.infer_uint8`)."""
-    _require_cuda(image)
+    dev = _device(image)
     if image.dim() != 3 or image.shape[-1] != 3 or image.dtype not in (torch.uint8, torch.float32):
         raise ValueError(f"expected an (H, W, 3) uint8 or float32 image, got {tuple(image.shape)} {image.dtype}")
     H, W = image.shape[:2]
@@ -120,9 +117,9 @@ def split_panorama_image(image: torch.Tensor, extrinsics, intrinsics, resolution
         raise ValueError(f"need a non-empty image of at most 2^29 pixels and 1 <= resolution <= 16384, got {H} x {W}, resolution {resolution}")
     E, K = _cameras(extrinsics, intrinsics)
     img = image.contiguous()
-    out = torch.empty((len(E), resolution, resolution, 3), device=img.device, dtype=img.dtype)
-    with torch.cuda.device(img.device):
-        L.check(L.lib.moge_pano_split(img.data_ptr(), int(img.dtype == torch.uint8), H, W, _hp(E), _hp(K), len(E), resolution, out.data_ptr(), L.stream_ptr(img.device)))
+    out = torch.empty((len(E), resolution, resolution, 3), device=dev, dtype=img.dtype)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_pano_split(ptr(img), int(img.dtype == torch.uint8), H, W, _hp(E), _hp(K), len(E), resolution, ptr(out), st))
     return out
 
 
@@ -134,15 +131,15 @@ def _views(distance_maps, pred_masks):
         distance_maps = list(distance_maps)
         if len(distance_maps) == 0:
             raise ValueError("need at least one view (n == 0)")
-        _require_cuda(*distance_maps)
+        _device(*distance_maps)
         distance_maps = torch.stack(distance_maps)
     if not isinstance(pred_masks, torch.Tensor):
         pred_masks = list(pred_masks)
         if len(pred_masks) == 0:
             raise ValueError("need at least one view (n == 0)")
-        _require_cuda(*pred_masks)
+        _device(*pred_masks)
         pred_masks = torch.stack(pred_masks)
-    _require_cuda(distance_maps, pred_masks)
+    _device(distance_maps, pred_masks)
     if distance_maps.dim() != 3 or distance_maps.dtype != torch.float32:
         raise ValueError(f"distance_maps must be (n, h, w) float32, got {tuple(distance_maps.shape)} {distance_maps.dtype}")
     if pred_masks.shape != distance_maps.shape or pred_masks.dtype not in (torch.bool, torch.uint8):
@@ -169,13 +166,12 @@ def _system(width, height, dist, masks, E, K, _ws=None) -> PanoSystem:
     n, vh, vw = dist.shape
     dev = dist.device
     M = system_rows(width, height)
-    with torch.cuda.device(dev):
-        ws = _ws if _ws is not None else torch.empty(workspace_bytes(width, height, n), device=dev, dtype=torch.uint8)
-        b = torch.empty(M, device=dev, dtype=torch.float64)
-        rows = torch.empty(M, device=dev, dtype=torch.uint8)
-        seen = torch.empty((height, width), device=dev, dtype=torch.uint8)
-        L.check(L.lib.moge_pano_system(width, height, dist.data_ptr(), masks.data_ptr(), n, vh, vw, _hp(E), _hp(K), ws.data_ptr(), b.data_ptr(), rows.data_ptr(),
-                                       seen.data_ptr(), L.stream_ptr(dev)))
+    ws = _ws if _ws is not None else torch.empty(workspace_bytes(width, height, n), device=dev, dtype=torch.uint8)
+    b = torch.empty(M, device=dev, dtype=torch.float64)
+    rows = torch.empty(M, device=dev, dtype=torch.uint8)
+    seen = torch.empty((height, width), device=dev, dtype=torch.uint8)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_pano_system(width, height, ptr(dist), ptr(masks), n, vh, vw, _hp(E), _hp(K), ptr(ws), ptr(b), ptr(rows), ptr(seen), st))
     return PanoSystem(width, height, b, rows, seen.view(torch.bool))
 
 
@@ -185,13 +181,13 @@ def lsmr(system: PanoSystem, x0: Optional[torch.Tensor] = None, atol: float = 1e
     recurrences, stopping rule and return values: -> x (width * height,) float64 CUDA, istop, itn, normr, normar, normA, condA, normx.
     maxiter None: min(selected rows, pixels).  The host reads the solver's state once per `poll` iterations; the result does not depend on
     `poll`, and two calls give the same bits."""
-    _require_cuda(system.b, system.rows)
+    dev = _device(system.b, system.rows)
     W, H = system.width, system.height
     N, M = W * H, system_rows(W, H)
     if system.b.shape != (M,) or system.b.dtype != torch.float64 or system.rows.shape != (M,) or system.rows.dtype != torch.uint8:
         raise ValueError(f"a {W} x {H} system has b float64 and rows uint8 of {M} entries")
     if x0 is not None:
-        _require_cuda(x0)
+        _device(system.b, x0)
         if x0.numel() != N or x0.dtype != torch.float64:
             raise ValueError(f"x0 must hold {N} float64 values")
         x0 = x0.reshape(-1).contiguous()
@@ -199,27 +195,28 @@ def lsmr(system: PanoSystem, x0: Optional[torch.Tensor] = None, atol: float = 1e
         raise ValueError("maxiter must be >= 1 (or None)")
     if not 1 <= int(poll) <= 65536:
         raise ValueError("poll must be 1 ... 65536")
-    dev = system.b.device
     info = (C.c_double * 8)()
-    with torch.cuda.device(dev):
-        ws = _ws if _ws is not None else torch.empty(workspace_bytes(W, H, 0), device=dev, dtype=torch.uint8)
-        x = torch.empty(N, device=dev, dtype=torch.float64)
-        L.check(L.lib.moge_pano_lsmr(W, H, system.b.contiguous().data_ptr(), system.rows.contiguous().data_ptr(), x0.data_ptr() if x0 is not None else None,
-                                     float(atol), float(btol), float(conlim), int(maxiter or 0), int(poll), ws.data_ptr(), x.data_ptr(), info, L.stream_ptr(dev)))
+    ws = _ws if _ws is not None else torch.empty(workspace_bytes(W, H, 0), device=dev, dtype=torch.uint8)
+    x = torch.empty(N, device=dev, dtype=torch.float64)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_pano_lsmr(W, H, ptr(system.b.contiguous()), ptr(system.rows.contiguous()), ptr(x0), float(atol), float(btol), float(conlim),
+                                     int(maxiter or 0), int(poll), ptr(ws), ptr(x), info, st))
     return x, int(info[0]), int(info[1]), info[2], info[3], info[4], info[5], info[6]
 
 
 def _resize_bilinear(src: torch.Tensor, height: int, width: int) -> torch.Tensor:
     H, W = src.shape
     out = torch.empty((height, width), device=src.device, dtype=torch.float32)
-    L.check(L.lib.moge_pano_resize_bilinear(src.contiguous().data_ptr(), H, W, height, width, out.data_ptr(), L.stream_ptr(src.device)))
+    with L.on(src.device) as st:
+        L.check(L.lib.moge_pano_resize_bilinear(ptr(src.contiguous()), H, W, height, width, ptr(out), st))
     return out
 
 
 def _resize_nearest(src: torch.Tensor, height: int, width: int) -> torch.Tensor:
     H, W = src.shape
     out = torch.empty((height, width), device=src.device, dtype=torch.uint8)
-    L.check(L.lib.moge_pano_resize_nearest(src.contiguous().view(torch.uint8).data_ptr(), H, W, height, width, out.data_ptr(), L.stream_ptr(src.device)))
+    with L.on(src.device) as st:
+        L.check(L.lib.moge_pano_resize_nearest(ptr(src.contiguous().view(torch.uint8)), H, W, height, width, ptr(out), st))
     return out.view(torch.bool)
 
 
@@ -236,11 +233,13 @@ def _merge(width, height, dist, masks, E, K, poll, itns):
     x0 = None
     if init is not None:
         x0 = torch.empty(width * height, device=dev, dtype=torch.float64)
-        L.check(L.lib.moge_pano_log(init.data_ptr(), width * height, x0.data_ptr(), L.stream_ptr(dev)))
+        with L.on(dev) as st:
+            L.check(L.lib.moge_pano_log(ptr(init), width * height, ptr(x0), st))
     x, _, itn, *_ = lsmr(system, x0=x0, atol=1e-5, btol=1e-5, poll=poll, _ws=ws)
     itns.append(itn)
     distance = torch.empty((height, width), device=dev, dtype=torch.float32)
-    L.check(L.lib.moge_pano_finish(x.data_ptr(), distance.data_ptr(), height, width, None, L.stream_ptr(dev)))
+    with L.on(dev) as st:
+        L.check(L.lib.moge_pano_finish(ptr(x), ptr(distance), height, width, None, st))
     return distance, system.seen
 
 
@@ -254,8 +253,7 @@ def merge_panorama_depth(width: int, height: int, distance_maps, pred_masks, ext
     dist, masks = _views(distance_maps, pred_masks)
     _check_map(width, height)
     E, K = _cameras(extrinsics, intrinsics, dist.shape[0])
-    with torch.cuda.device(dist.device):
-        return _merge(width, height, dist, masks, E, K, int(poll), iterations if iterations is not None else [])
+    return _merge(width, height, dist, masks, E, K, int(poll), iterations if iterations is not None else [])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -272,11 +270,10 @@ def infer_panorama(model, image_u8: torch.Tensor, resolution: int = 512, batch_s
     host pipeline's bit for bit.  image_u8 (H, W, 3) uint8 CUDA.  Returns CUDA tensors: distance (H, W) float32, mask (H, W) bool, points
     (H, W, 3) float32, and the per-view intermediates "views" (n, res, res, 3) uint8, "view_distance" (n, res, res) float32, "view_mask"
     (n, res, res) bool."""
-    _require_cuda(image_u8)
+    dev = _device(image_u8)
     if image_u8.dim() != 3 or image_u8.shape[-1] != 3 or image_u8.dtype != torch.uint8:
         raise ValueError(f"expected an (H, W, 3) uint8 image, got {tuple(image_u8.shape)} {image_u8.dtype}")
     H, W = image_u8.shape[:2]
-    dev = image_u8.device
     E, Ks = get_panorama_cameras()
     views = split_panorama_image(image_u8, E, Ks, resolution)
     fov = intrinsics_to_fov_x_deg(np.array(Ks))
@@ -293,9 +290,9 @@ def infer_panorama(model, image_u8: torch.Tensor, resolution: int = 512, batch_s
     view_dist, view_mask = torch.cat(dist).float(), torch.cat(masks)
     mw, mh = min(merge_size[0], W), min(merge_size[1], H)
     distance, mask = merge_panorama_depth(mw, mh, view_dist, view_mask, E, Ks)
-    with torch.cuda.device(dev):
-        distance = _resize_bilinear(distance, H, W)
-        mask = _resize_nearest(mask, H, W)
-        points = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
-        L.check(L.lib.moge_pano_finish(None, distance.data_ptr(), H, W, points.data_ptr(), L.stream_ptr(dev)))
+    distance = _resize_bilinear(distance, H, W)
+    mask = _resize_nearest(mask, H, W)
+    points = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
+    with L.on(dev) as st:
+        L.check(L.lib.moge_pano_finish(None, ptr(distance), H, W, ptr(points), st))
     return {"distance": distance, "mask": mask, "points": points, "views": views, "view_distance": view_dist, "view_mask": view_mask}

@@ -16,13 +16,10 @@ from typing import Optional
 import torch
 
 from . import _lib as L
+from ._lib import ptr
 
 TILE = 32                   # csrc/refine.hip REFINE_TILE: the square output tile of one workgroup (the tests place shapes around it)
 KERNEL_SIZES = (3, 5, 7)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def refine_depth_with_normal(depth: torch.Tensor, normal: torch.Tensor, intrinsics: torch.Tensor, iterations: int = 10, damp: float = 1e-3,
@@ -39,9 +36,7 @@ def refine_depth_with_normal(depth: torch.Tensor, normal: torch.Tensor, intrinsi
     non-finite depth, and rays perpendicular to the normal (n_z + n_xy . (Kinv[:2,:2] uv + Kinv[:2,2]) = 0, a zero denominator of the
     gradient).  With a mask the same holds for the masked-in pixels.  kernel_size is 3, 5 or 7 and H, W >= kernel_size (ValueError otherwise).
     The call does not synchronise with the host."""
-    for t in (depth, normal, intrinsics, mask):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("moge_amd.refine works on GPU tensors only (no CPU path)")
+    dev = L.device_of("refine", depth, normal, intrinsics, mask)
     if kernel_size not in KERNEL_SIZES:
         raise ValueError(f"kernel_size must be one of {KERNEL_SIZES}, got {kernel_size}")
     if depth.dim() < 2 or normal.shape[-1] != 3 or normal.shape[:-1] != depth.shape or intrinsics.shape[-2:] != (3, 3):
@@ -63,9 +58,9 @@ def refine_depth_with_normal(depth: torch.Tensor, normal: torch.Tensor, intrinsi
     out = torch.empty_like(d)
     if B:
         nbytes = C.c_int64(0)
-        with torch.cuda.device(d.device):
-            L.check(L.lib.moge_refine_depth_workspace(B, H, W, C.byref(nbytes)))
-            ws = torch.empty(nbytes.value, device=d.device, dtype=torch.uint8)
-            L.check(L.lib.moge_refine_depth(_p(d), _p(n), _p(k), _p(m), B, H, W, int(kernel_size), int(iterations), float(damp), float(eps), _p(ws),
-                                            _p(out), L.stream_ptr(d.device)))
+        L.check(L.lib.moge_refine_depth_workspace(B, H, W, C.byref(nbytes)))
+        ws = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+        with L.on(dev) as st:
+            L.check(L.lib.moge_refine_depth(ptr(d), ptr(n), ptr(k), ptr(m), B, H, W, int(kernel_size), int(iterations), float(damp), float(eps), ptr(ws),
+                                            ptr(out), st))
     return out.reshape(depth.shape).to(depth.dtype)

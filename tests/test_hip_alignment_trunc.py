@@ -189,8 +189,8 @@ def test_anchored_row_alone_equals_row_in_batch(A, n, d, mask):
         m = rb.numel()
         out = [torch.empty(m, device="cuda"), torch.empty(m, device="cuda"), torch.empty(m, device="cuda", dtype=torch.int32)]
         ws = A._trunc_workspace(n * d, m, src.device)
-        L.check(L.lib.moge_align_trunc_anchored(A._p(src), A._p(tgt), A._p(w), n, d, mask, A._p(rb), A._p(rk), m, 0.1, 1e-7, A._p(ws), *(A._p(o) for o in out),
-                                                A._stream()))
+        L.check(L.lib.moge_align_trunc_anchored(L.ptr(src), L.ptr(tgt), L.ptr(w), n, d, mask, L.ptr(rb), L.ptr(rk), m, 0.1, 1e-7, L.ptr(ws), *(L.ptr(o) for o in out),
+                                                L.stream_ptr(src.device)))
         return out
 
     batch = solve(rb, rk)

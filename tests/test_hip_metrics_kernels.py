@@ -290,10 +290,10 @@ def test_segment_stats_pack_error(M, kind):
     diameter = torch.empty(U, dtype=torch.float32, device="cuda")
     labels_t = _t(np.array(uniq, np.int32))
     index = _t(lr_i.astype(np.int32))
-    p = M._p
+    p = M.L.ptr
     m8, gt_t, lr8 = _t(mask.view(np.uint8)), _t(gt), _t(lr_m.view(np.uint8))            # held until the kernels have run
     M.L.check(M.L.lib.moge_metrics_segment_stats(p(seg32), p(m8), p(gt_t), H, W, p(lr8), p(index), 64, 64, p(labels_t), U, p(bbox), p(lr_count),
-                                                 p(diameter), M._stream()))
+                                                 p(diameter), M.L.stream_ptr(seg32.device)))
     bbox, lr_count, diameter = bbox.cpu().numpy().reshape(U, 6), lr_count.cpu().numpy(), diameter.cpu().numpy()
     for u, s in enumerate(ref):
         assert np.array_equal(bbox[u], s["bbox"]), (kind, u, bbox[u], s["bbox"])
