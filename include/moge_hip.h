@@ -250,9 +250,15 @@ int moge_profile_read(moge_handle* h, moge_profile* out, int reset);   /* synchr
  * Layout is the library's own (token-major / NHWC); *numel receives the element count. */
 int moge_debug_tap(moge_handle* h, const char* name, float* dst, int64_t dst_capacity, int64_t* numel, void* stream);
 
-/* Runtime tuning / A-B switches (same keys as the MOGE_<KEY> environment variables; tests and tools only):
- *   GEMM_PP, PP_ROW128, ATTN_PP, ATTN_NW, BATCH_SPLIT, GLDS_VARIANT, ...   The library's defaults are the tuned ones. */
-void moge_tune_set(const char* key, int value);
+/* Runtime tuning / A-B switches (tests and tools only).  The keys of a build and their defaults - the tuned ones - are the table of
+ * moge_amd/csrc/tune.h; INTEGRATION.md section 6 gives their meanings.  Process-global, shared by every handle, safe from several host threads.
+ * MOGE_<KEY> in the environment is read once per process.  A key the build does not have -> MOGE_ERR_INVALID, moge_last_error() names it.
+ *   moge_tune_set    the value launches read from now on
+ *   moge_tune_reset  back to MOGE_<KEY> where the environment set it, else to the table's default; key == NULL: every key
+ *   moge_tune_value  *value = what a launch would read now (a negative default whose value the call site derives is returned as stored) */
+int moge_tune_set(const char* key, int value);
+int moge_tune_reset(const char* key);
+int moge_tune_value(const char* key, int* value);
 
 /* ---- per-kernel test entry points (stage-level parity; tests/ only) -------------------------------- */
 /* C[M,N] = A[M,K] * W[N,K]^T + bias, fp32 in/out on device; computed in `precision`. act: 0 none 1 relu 2 gelu */

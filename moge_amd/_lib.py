@@ -133,7 +133,9 @@ SIGNATURES = {
     "moge_profile_enable": (C.c_int, [_vp, _i32]),
     "moge_profile_read": (C.c_int, [_vp, C.POINTER(Profile), _i32]),
     "moge_debug_tap": (C.c_int, [_vp, C.c_char_p, _vp, _i64, C.POINTER(_i64), _vp]),
-    "moge_tune_set": (None, [C.c_char_p, _i32]),
+    "moge_tune_set": (C.c_int, [C.c_char_p, _i32]),
+    "moge_tune_reset": (C.c_int, [C.c_char_p]),
+    "moge_tune_value": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "moge_test_gemm": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _vp]),
     "moge_test_gemm_ex": (C.c_int, [C.POINTER(TestGemmArgs), _vp]),
     "moge_test_layernorm": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _vp]),
@@ -235,9 +237,47 @@ def check(code: int) -> None:
     raise MogeError(f"libmoge_hip error {code}: {msg}")
 
 
+# ---- A/B switches (tests / tools): the keys of csrc/tune.h = the MOGE_<KEY> environment variables; all act on the currently selected `lib` ----
 def tune(key: str, value: int) -> None:
-    """A/B switch of the library (tests / tools): same keys as the MOGE_<KEY> environment variables."""
-    lib.moge_tune_set(key.encode(), int(value))
+    """Set a switch.  A key the library does not have raises MogeError."""
+    check(lib.moge_tune_set(key.encode(), int(value)))
+
+
+def tune_reset(key: str = None) -> None:
+    """A switch (None: every switch) back to its MOGE_<KEY> value where the environment set one, else to the table's default."""
+    check(lib.moge_tune_reset(None if key is None else key.encode()))
+
+
+def tune_value(key: str) -> int:
+    """What a launch would read now."""
+    v = C.c_int()
+    check(lib.moge_tune_value(key.encode(), C.byref(v)))
+    return v.value
+
+
+class tuned:
+    """`with tuned(ATTN_KS=0, PP_MIN_TILES=0):` sets the given switches and on exit resets exactly those (tune_reset), whatever tune() calls
+    happened inside - also when the body raises.  Blocks on the same key do not nest: the inner block's exit resets the key, it does not
+    return it to the outer block's value."""
+
+    def __init__(self, **keys: int):
+        self.keys = keys
+
+    def __enter__(self) -> "tuned":
+        done = []
+        try:
+            for k, v in self.keys.items():
+                tune(k, v)
+                done.append(k)
+        except MogeError:                 # an unknown key: leave nothing set behind
+            for k in done:
+                tune_reset(k)
+            raise
+        return self
+
+    def __exit__(self, *exc) -> None:
+        for k in self.keys:
+            tune_reset(k)
 
 
 def stream_ptr(device=None) -> int:

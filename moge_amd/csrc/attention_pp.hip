@@ -72,8 +72,6 @@ constexpr float AP_PSUM_LIMIT = 16384.f;
 //      sums: the decision is known right after the K Q^T chain, so the exponentials are free to interleave with the P V MFMAs (with the
 //      sum-based guard the branch sits between the last exponential and the first P V MFMA and serialises the two)
 constexpr int AP_VAR_DEFAULT = 0;
-constexpr int AP_X_DEFAULT = 0;         // attn_pp16x_kernel (round 5, --experiments builds only): measured 13 % slower than attn_pp16mq<4>
-constexpr int AP_KERN_DEFAULT = 3;      // 0: attn_pp16_kernel; 1 / 2 / 3: attn_pp16mq_kernel<2> / <4> / chosen by grid size (row sums on the matrix pipe)
 constexpr float AP_SCORE_LIMIT = 15.f;
 constexpr float AP_ROWSUM_LIMIT = 49152.f;      // attn_pp16m: FULL row sum of a tile (64 keys) below this -> every P < 49152 < 65504 (fp16 max)
 template <int VAR>
@@ -822,24 +820,26 @@ static int launch_attn_pp16(const void* q, const void* k, const void* v, void* o
     // attn_pp16mq_kernel<QB>: row sums on the matrix pipe; QB = 4 (64 queries per wave, 2 waves per SIMD) when the grid still fills the chip
     // several times over, QB = 2 (3 waves per SIMD) otherwise - bit-identical results (see the kernel).  ATTN_KERN: 0 = attn_pp16_kernel,
     // 1 = QB 2 always, 2 = QB 4 always, 3 (default) = by grid size
-    const int akern = moge_tune_get("ATTN_KERN", AP_KERN_DEFAULT);
+    const int akern = moge_tune_get(TK_ATTN_KERN);
     if (akern >= 1) {
         // QB = 2 while its grid fits ONE round of the chip (3 workgroups per CU): a lone round is a latency chain per workgroup and the 32-query
         // form's is the shorter one (N = 3601, one image: 464 workgroups, 720 vs 680 TF/s; N = 1370 x 4: 760 vs 631); from two images on the
         // 64-query form wins (928 workgroups = 1.2 rounds against 480 = 0.94: 745-797 vs 845-879 TF/s; r03zd_kbench_attn_b1.log)
         const long wgs2 = (long)((Ntok + 127) / 128) * B * nh;
-        const bool q4 = akern == 2 || akern == 4 || (akern == 3 && wgs2 > moge_tune_get("ATTN_Q2_MAX_WGS", 3 * pp_device_cus()));
+        int q2_max = moge_tune_get(TK_ATTN_Q2_MAX_WGS);
+        if (q2_max < 0) q2_max = 3 * pp_device_cus();           // (the table's default)
+        const bool q4 = akern == 2 || akern == 4 || (akern == 3 && wgs2 > q2_max);
         constexpr int xr = 3;           // the kernels' xcd_remap argument: bit 0 = a head's query blocks on one XCD, bit 1 = the short tail of attn_pp16mq<4> (both always on)
 #ifdef MOGE_EXPERIMENTS
         // attn_pp16x_kernel (ping-pong wave groups, 512 queries per workgroup, ONE workgroup per CU): bit-identical to the two above; taken while
         // its grid still fills the chip at least ATTN_X_MIN_ROUNDS (default 2) times.  ATTN_KERN 4 forces it, ATTN_X = 0 switches it off.
         const int nfull = Ntok / 512, rem = Ntok - nfull * 512;
         const int nblk = nfull + (rem > 256 ? 1 : 0);                 // a block more than half full runs here, a smaller rest on attn_pp16mq
-        const bool xk = nblk > 0 && (akern == 4 || (akern == 3 && moge_tune_get("ATTN_X", AP_X_DEFAULT) &&
-                                                    (long)nblk * B * nh >= (long)moge_tune_get("ATTN_X_MIN_ROUNDS", 2) * pp_device_cus()));
+        const bool xk = nblk > 0 && (akern == 4 || (akern == 3 && moge_tune_get(TK_ATTN_X) &&
+                                                    (long)nblk * B * nh >= (long)moge_tune_get(TK_ATTN_X_MIN_ROUNDS) * pp_device_cus()));
         if (xk) {
             constexpr int smem_x = 4 * AP_STAGE + 8 * 8192;
-            if (moge_tune_get("ATTN_X_TS", 0)) {                // tools only: segment timeline of one workgroup (see the kernel)
+            if (moge_tune_get(TK_ATTN_X_TS)) {                // tools only: segment timeline of one workgroup (see the kernel)
                 static unsigned long long* dts = nullptr;
                 if (!dts && hipMalloc(&dts, 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
                 (void)hipMemsetAsync(dts, 0, 16 * sizeof(unsigned long long), st);
@@ -852,7 +852,7 @@ static int launch_attn_pp16(const void* q, const void* k, const void* v, void* o
                     if (h[g2 * 8 + 4])
                         fprintf(stderr, "[attn_pp16x ts] group %d: %llu hot tiles; per tile (s_memtime ticks): E body %.0f, barrier wait %.0f, M body %.0f, barrier wait %.0f\n", g2, h[g2 * 8 + 4],
                                 (double)h[g2 * 8 + 0] / h[g2 * 8 + 4], (double)h[g2 * 8 + 1] / h[g2 * 8 + 4], (double)h[g2 * 8 + 2] / h[g2 * 8 + 4], (double)h[g2 * 8 + 3] / h[g2 * 8 + 4]);
-            } else if (moge_tune_get("ATTN_X_PRIO", 0)) {
+            } else if (moge_tune_get(TK_ATTN_X_PRIO)) {
                 if (int rc = set_dyn_lds<attn_pp16x_kernel<1>>(smem_x)) return rc;
                 hipLaunchKernelGGL(attn_pp16x_kernel<1>, dim3(nblk, B * nh), dim3(512), smem_x, st, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, Ntok, nh, xr);
             } else {
@@ -892,13 +892,13 @@ static int launch_attn_pp16(const void* q, const void* k, const void* v, void* o
         // attn_pp16ks_kernel: grids of at most ONE 4-wave workgroup per CU run as 8-wave workgroups with the key range split inside the workgroup
         // (two waves per SIMD, half the serial tiles; see the kernel).  32-query blocks while they fit the chip (more CUs busy), else 64-query blocks
         // (N = 3601, 16 heads, one image: 464 > 256 >= 240).  ATTN_KS: 0 off (a single image is then bit-identical to a batch item), 1 by grid size (default), 2 / 4 forced (tests)
-        if (const int ks = moge_tune_get("ATTN_KS", 1); ks > 1 || (ks == 1 && akern == 3)) {
+        if (const int ks = moge_tune_get(TK_ATTN_KS); ks > 1 || (ks == 1 && akern == 3)) {
             constexpr int smem_ks = 6 * AP_STAGE;
             const int cus = pp_device_cus(), ntiles = (Ntok + 63) >> 6;
             const long w2 = (long)((Ntok + 127) / 128) * B * nh, w4 = (long)((Ntok + 255) / 256) * B * nh;
             const bool fits = ks == 1 && ntiles >= AP_KS_MIN_TILES;
             int tmid = (ntiles + 1) >> 1;
-            if (const int f = moge_tune_get("ATTN_KS_MID", 0); f > 0 && f < ntiles) tmid = f;       // tests / tools: any split point
+            if (const int f = moge_tune_get(TK_ATTN_KS_MID); f > 0 && f < ntiles) tmid = f;       // tests / tools: any split point
             if ((ks == 2 && ntiles >= 2) || (fits && w2 <= cus)) {
                 if (int rc = set_dyn_lds<attn_pp16ks_kernel<2>>(smem_ks)) return rc;
                 hipLaunchKernelGGL(attn_pp16ks_kernel<2>, dim3((Ntok + 127) / 128, B * nh), dim3(512), smem_ks, st, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, Ntok, nh, xr, tmid);
@@ -923,7 +923,7 @@ static int launch_attn_pp16(const void* q, const void* k, const void* v, void* o
         hipLaunchKernelGGL(attn_pp16_kernel<V>, grid, dim3(256), smem, st, (const f16*)q, (const f16*)k, (const f16*)v, (f16*)out, Ntok, nh); \
         return (int)hipGetLastError(); } while (0)
 #ifdef MOGE_EXPERIMENTS
-    switch (moge_tune_get("ATTN_VAR", AP_VAR_DEFAULT)) {       // tools/kbench A-B only
+    switch (moge_tune_get(TK_ATTN_VAR)) {       // tools/kbench A-B only
     case 0: AP_LAUNCH_VAR(0);
     case 1: AP_LAUNCH_VAR(1);
     case 2: AP_LAUNCH_VAR(2);
@@ -962,7 +962,7 @@ static int launch_attn_pp_cfg(const void* q, const void* k, const void* v, void*
 int launch_attention_pp(const void* q, const void* k, const void* v, void* out, int B, int nh, int Ntok, hipStream_t st, void* ws, size_t ws_bytes) {
     if (Ntok < 1) return -1;
 #ifdef MOGE_EXPERIMENTS
-    switch (moge_tune_get("ATTN_EXP", 0)) {            // tools/kbench A-B only
+    switch (moge_tune_get(TK_ATTN_EXP)) {            // tools/kbench A-B only
     case 1: return launch_attn_pp_cfg<4, 1>(q, k, v, out, B, nh, Ntok, st);
     case 2: return launch_attn_pp_cfg<4, 2>(q, k, v, out, B, nh, Ntok, st);
     case 3: return launch_attn_pp_cfg<8, 1>(q, k, v, out, B, nh, Ntok, st);

@@ -314,5 +314,4 @@ int launch_ct3_combine(const float* P, const Ct3Slot* slots_dev, int nslots, int
 int launch_ct3_border(const void* in, const void* dw, void* out, int B, int H, int W, int Cin, int Cout, hipStream_t st);
 bool conv_rb_eligible(const GemmArgs& g);   // conv_rb.hip: fp16 residual block with the intermediate map kept in LDS (C = 64)
 int launch_conv_rb(const GemmArgs& g, hipStream_t st);
-// runtime tuning / A-B switches (tests, tools/kbench): see tune.cpp-style table in gemm.hip
-int moge_tune_get(const char* key, int dflt);
+#include "tune.h"       // runtime tuning / A-B switches (tests, tools/kbench): the table of keys and defaults, moge_tune_get(TK_<KEY>)

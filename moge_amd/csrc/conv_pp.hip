@@ -633,7 +633,7 @@ int launch_conv_cfg(const GemmArgs& g, hipStream_t st) {
     // persistent: as many workgroups as the chip holds at once (LDS: two per CU for the single-image 64-channel form, one otherwise)
     const int ncu = pp_device_cus();
     long slots = (BN == 64 && NH == 1) ? tiles : (long)ncu;          // (the two-per-CU form: one tile per workgroup, see PERSIST)
-    const long cap = moge_tune_get("CONV_GRID", 0);      // tests: a small grid makes small problems walk many tiles per workgroup
+    const long cap = moge_tune_get(TK_CONV_GRID);      // tests: a small grid makes small problems walk many tiles per workgroup
     if (cap > 0 && !(BN == 64 && NH == 1)) slots = cap;
     const long grid = tiles < slots ? tiles : slots;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, g);
@@ -680,7 +680,7 @@ static int launch_conv_epi(const GemmArgs& g, hipStream_t st) {
         }
     }
 #ifdef MOGE_EXPERIMENTS
-    if (TW == 32 || moge_tune_get("CONV_M16", 1) == 0) {       // the v_mfma_f32_32x32x16_f16 form (tools/kbench A-B only)
+    if (TW == 32 || moge_tune_get(TK_CONV_M16) == 0) {       // the v_mfma_f32_32x32x16_f16 form (tools/kbench A-B only)
         switch (e) {
         case 0: return launch_conv_cfg<BN, TW, NH, 0>(g, st);
         case 1: return launch_conv_cfg<BN, TW, NH, 1>(g, st);
@@ -804,12 +804,12 @@ int launch_conv_pp(const GemmArgs& g, hipStream_t st) {
         return g.uv.wu ? launch_conv_cfg<128, 16, 2, 8 | 2 | 64 | 1>(g, st) : launch_conv_cfg<128, 16, 2, 8 | 2 | 64>(g, st);
     }
     // a single halo image: one buffer.  A 64-channel layer with a side input runs on the single-buffer form too (side fragments in registers)
-    const bool side_reg = g.C == 64 && g.N == 64 && g.a2 && !g.uv.wu && !g.relu_in && g.epi == EPI_STORE && moge_tune_get("CONV_SIDE_REG", 1);
+    const bool side_reg = g.C == 64 && g.N == 64 && g.a2 && !g.uv.wu && !g.relu_in && g.epi == EPI_STORE && moge_tune_get(TK_CONV_SIDE_REG);
     const bool one_image = g.C == 64 && (!g.a2 || side_reg);
     if (g.N == 64) {
         // 32-pixel-wide tiles (64 px x 64 ch per wave) when the image is wide enough to fill them
 #ifdef MOGE_EXPERIMENTS
-        if (one_image && g.W >= 32 && moge_tune_get("CONV_TW32", 0)) return launch_conv_epi<64, 32, 1>(g, st);
+        if (one_image && g.W >= 32 && moge_tune_get(TK_CONV_TW32)) return launch_conv_epi<64, 32, 1>(g, st);
 #endif
         return one_image ? launch_conv_epi<64, 16, 1>(g, st) : launch_conv_epi<64, 16, 2>(g, st);
     }

@@ -403,7 +403,7 @@ int launch_layernorm(const float* x, const float* w, const float* b, void* out, 
                      int tap_mode, int Ntok, hipStream_t st) {
     if (D % 4 != 0 || D > 1024 || (ldo & 3) || (coloff & 3)) return -1;
 #ifdef MOGE_EXPERIMENTS
-    if (sizeof(T) == 2 && moge_tune_get("LN_LOWREG", 0)) {
+    if (sizeof(T) == 2 && moge_tune_get(TK_LN_LOWREG)) {
         hipLaunchKernelGGL(layernorm_lr_kernel<T>, dim3((unsigned)((rowsN + 15) / 16)), dim3(256), 0, st, x, w, b, (T*)out, cls_out, rowsN, D, ldo, coloff,
                            tap_mode, Ntok);
         return (int)hipGetLastError();

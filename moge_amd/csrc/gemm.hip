@@ -679,33 +679,7 @@ static int launch_cfg(const GemmArgs& g, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-// ---- runtime tuning switches: environment (MOGE_<KEY>) overridden by moge_tune_set(key, value) -------------------------
-// Process-global and shared by every handle: guarded by a mutex (two handles on two host threads = one GPU each is a supported
-// deployment).  A switch that the ENVIRONMENT moves off its default is announced once on stderr: production must not be re-routed
-// to a non-default kernel silently.
-#include <map>
-#include <mutex>
-#include <string>
 #include <type_traits>
-#include <cstdio>
-static std::map<std::string, int>& tune_table() { static std::map<std::string, int> t; return t; }
-static std::mutex& tune_mutex() { static std::mutex m; return m; }
-int moge_tune_get(const char* key, int dflt) {
-    std::lock_guard<std::mutex> lk(tune_mutex());
-    auto& t = tune_table();
-    auto it = t.find(key);
-    if (it != t.end()) return it->second;
-    const std::string env = std::string("MOGE_") + key;
-    const char* e = getenv(env.c_str());
-    const int v = e ? atoi(e) : dflt;
-    if (e && v != dflt) fprintf(stderr, "[libmoge_hip] %s=%d overrides the tuned default (%d): non-default kernel selection\n", env.c_str(), v, dflt);
-    t[key] = v;                        // cache: launches look switches up on every call
-    return v;
-}
-extern "C" void moge_tune_set(const char* key, int value) {
-    std::lock_guard<std::mutex> lk(tune_mutex());
-    tune_table()[key] = value;
-}
 
 template <typename T, int AMODE>
 static int launch_by_n(const GemmArgs& g, hipStream_t st) {
@@ -717,11 +691,11 @@ static int launch_by_n(const GemmArgs& g, hipStream_t st) {
 // latency regime (batch 1): fewer than half a wave of 256x256 tiles leaves most CUs idle; the 128x128 / 64x128 kernels below have 4-8x the
 // workgroups (measured at M = 3601: proj 24 vs 33 us, fc2 56 vs 90 us)
 bool gemm_runs_pp(const GemmArgs& g) {
-    if (!moge_tune_get("GEMM_PP", 1) || !gemm_pp_eligible(g)) return false;
+    if (!moge_tune_get(TK_GEMM_PP) || !gemm_pp_eligible(g)) return false;
     const long tiles = ((long)(g.M + 255) / 256) * ((g.N + 255) / 256);
     // crossover (M = 3601 per image, N = 1024): the 64 x 128 kernel takes 47 / 18 us per image (fc2 / proj), a 256 x 256 tile 74 / 28 us however few of
     // them there are - from ~94 tiles (two images: 116) the throughput kernel wins (batch 2: 169.3 -> 173.4 img/s)
-    return tiles >= moge_tune_get("PP_MIN_TILES", 96);
+    return tiles >= moge_tune_get(TK_PP_MIN_TILES);
 }
 
 // The shapes of AMODE_LINEAR that gemm_glds_kernel takes (when the ping-pong kernel does not: gemm_runs_pp)
@@ -753,14 +727,14 @@ int launch_gemm(const GemmArgs& g, int amode, hipStream_t st) {
             // ring = 72 KiB LDS, two co-resident workgroups per CU: at batch 1-2 the weights arrive cold from HBM and the second slab in flight is worth
             // more than a third workgroup - 7.3 -> 6.85 ms per image against the double buffer).  Same MFMA and K order: results are bit-identical.
             const long blocks128 = ((long)(g.M + 127) / 128) * ((g.N + 127) / 128);
-            if (blocks128 < moge_tune_get("GLDS_SMALL_BLOCKS", 512) && moge_tune_get("GLDS_VARIANT", 2) == 2) {
-                switch (moge_tune_get("GLDS_SMALL_NS", 3)) {            // ring depth of the 64x128 kernel (bit-identical results)
+            if (blocks128 < moge_tune_get(TK_GLDS_SMALL_BLOCKS) && moge_tune_get(TK_GLDS_VARIANT) == 2) {
+                switch (moge_tune_get(TK_GLDS_SMALL_NS)) {            // ring depth of the 64x128 kernel (bit-identical results)
                 case 3: return launch_glds<T, 2, 2, 1, 2, 3>(g, st);
                 case 4: return launch_glds<T, 2, 2, 1, 2, 4>(g, st);
                 default: return launch_glds<T, 2, 2, 1, 2, 2>(g, st);
                 }
             }
-            switch (moge_tune_get("GLDS_VARIANT", 2)) {
+            switch (moge_tune_get(TK_GLDS_VARIANT)) {
             case 1: return launch_glds<T, 2, 2, 2, 2, 1>(g, st);       // 128x128, single buffer
             case 2: return launch_glds<T, 2, 2, 2, 2, 2>(g, st);       // 128x128, double buffer
             case 4: return launch_glds<T, 2, 2, 2, 2, 3>(g, st);       // 128x128, 3-slab ring
@@ -771,7 +745,7 @@ int launch_gemm(const GemmArgs& g, int amode, hipStream_t st) {
         return launch_by_n<T, AMODE_LINEAR>(g, st);
     case AMODE_CONV3:
         if constexpr (std::is_same<T, f16>::value) {
-            if (moge_tune_get("CONV_PP", 1) && conv_pp_eligible(g)) return launch_conv_pp(g, st);
+            if (moge_tune_get(TK_CONV_PP) && conv_pp_eligible(g)) return launch_conv_pp(g, st);
         }
         // the fused output conv (GemmArgs::dot_tab, g.out == nullptr) exists in the halo kernel only: any other kernel would store the full
         // map through a null pointer.  Unsupported shape, not a launch.

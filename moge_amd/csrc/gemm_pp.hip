@@ -792,7 +792,6 @@ __device__ __forceinline__ void pp_epi_run(const GemmArgs& g, f32x4 (&acc)[8][4]
 // 64-127 of the wave ("hi") are read from LDS INSIDE the segment, into the registers of the "lo" fragments as those die, so the register
 // count does not change.  The DMA schedule is then tied to the global intervals (both groups issue at the start of an even interval - group 0
 // is in its read segment, group 1 in its MFMA segment - and wait at the interval ends), see the loop.
-constexpr int PP_WX_DEFAULT = 0;      // (measured slower in the production step: see launch_pp_any)
 template <int EPK, int SROWS, int MODE>
 __global__ __launch_bounds__(512, 2) void gemm_pp128p_kernel(const GemmArgs g) {
     constexpr bool MRG = MODE == 1;
@@ -1250,7 +1249,7 @@ static int launch_pp128p(const GemmArgs& g, hipStream_t st) {
     constexpr auto kern = gemm_pp128p_kernel<EPK, SROWS, MODE>;
     if (int rc = set_dyn_lds<kern>(smem)) return rc;
     const long ntiles = (long)((g.M + 255) / 256) * (g.N / 256);
-    long cap = moge_tune_get("PP_GRID", 0);                  // tests: a small grid makes small problems walk many tiles per workgroup
+    long cap = moge_tune_get(TK_PP_GRID);                  // tests: a small grid makes small problems walk many tiles per workgroup
     if (cap <= 0) cap = pp_num_cus();
     const long grid = ntiles < cap ? ntiles : cap;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, g);
@@ -1341,7 +1340,7 @@ static int epilogue_kind(const GemmArgs& g) {
 template <int EPK>
 static int launch_pp_any(const GemmArgs& g, hipStream_t st) {
 #ifdef MOGE_EXPERIMENTS
-    switch (moge_tune_get("PP_EXP", 0)) {              // tools/kbench A-B only
+    switch (moge_tune_get(TK_PP_EXP)) {              // tools/kbench A-B only
     case 1: return launch_pp128_cfg<EPK, 1>(g, st);
     case 2: return launch_pp128_cfg<EPK, 2>(g, st);
     case 3: return launch_pp128_cfg<EPK, 0>(g, st);
@@ -1351,14 +1350,14 @@ static int launch_pp_any(const GemmArgs& g, hipStream_t st) {
     default: break;
     }
 #endif
-    int kern = moge_tune_get("PP_KERN", -1);
+    int kern = moge_tune_get(TK_PP_KERN);
     if (kern < 0) kern = 2;
     // The product's persistent kernel is MODE 3 (round 4): the DMA pieces of a K-tile split 4 + 4 over the wave's two read segments (A(t+2) whole
     // in the first, W(t+2) in the second).  Same MFMAs in the same order as every other schedule: bit-identical results.
 #ifdef MOGE_EXPERIMENTS
     // MODE 7 (round 6, PP_WX; --experiments builds): the W stream continuous across the tile boundary; needs an even number of K-tiles >= 4.  Bit-identical; kbench,
     // sustained 1500-launch samples: qkv / fc1 / proj +1.2-1.4 %, fc2 level - and 247.1 -> 246.8 img/s in the production two-stream step (EXPERIMENTS R6.3d)
-    if (kern == 2 && pp_persistent_ok(g) && moge_tune_get("PP_WX", PP_WX_DEFAULT) != 0 && ((g.K >> 6) & 1) == 0 && g.K >= 256) return launch_pp128p<EPK, 64, 7>(g, st);
+    if (kern == 2 && pp_persistent_ok(g) && moge_tune_get(TK_PP_WX) != 0 && ((g.K >> 6) & 1) == 0 && g.K >= 256) return launch_pp128p<EPK, 64, 7>(g, st);
 #endif
     if (kern == 2 && pp_persistent_ok(g)) return launch_pp128p<EPK, 64, 3>(g, st);
 #ifdef MOGE_EXPERIMENTS
@@ -1380,13 +1379,13 @@ static int launch_pp_any(const GemmArgs& g, hipStream_t st) {
 
 int launch_gemm_pp(const GemmArgs& g0, hipStream_t st) {
     GemmArgs g = g0;
-    g.dbg = moge_tune_get("PP_DBG", 0);
+    g.dbg = moge_tune_get(TK_PP_DBG);
 #ifdef MOGE_EXPERIMENTS
-    g.abl = moge_tune_get("PP_ABL", 0);         // (the product build's kernels do not read it)
+    g.abl = moge_tune_get(TK_PP_ABL);         // (the product build's kernels do not read it)
 #else
     g.abl = 0;
 #endif
-    g.stagger = moge_tune_get("PP_STAGGER", 0);
+    g.stagger = moge_tune_get(TK_PP_STAGGER);
     g.stagger_clk = 56000;          // (only read when PP_STAGGER > 1)
     g.nt_store = 0;                 // plain stores: non-temporal ones for the streaming activations measured +-0 (EXPERIMENTS.md)
     switch (epilogue_kind(g)) {

@@ -755,7 +755,7 @@ static Plan make_plan(const moge_config& c, int prec, int B, int H, int W, int r
     int nheads = 0;
     for (int k = 0; k < 3; k++) nheads += (c.heads & HEAD_BITS[k]) ? 1 : 0;
     // (normalised residual blocks share ONE GroupNorm scratch per plan: heads then run one after the other)
-    p.head_sets = (nheads > 1 && moge_tune_get("HEAD_STREAMS", 1) != 0 && B <= moge_tune_get("HEAD_STREAMS_MAX_B", 1) && !stack_has_norm(c, false)) ? nheads : 1;      // (only the shared norm-statistics scratch `gn` serialises the heads: activation-only blocks keep their streams)
+    p.head_sets = (nheads > 1 && moge_tune_get(TK_HEAD_STREAMS) != 0 && B <= moge_tune_get(TK_HEAD_STREAMS_MAX_B) && !stack_has_norm(c, false)) ? nheads : 1;      // (only the shared norm-statistics scratch `gn` serialises the heads: activation-only blocks keep their streams)
     // (head streams: one triple more than heads - in the pipelined form triple 0 stays with the neck, which is still running when the first head starts)
     for (int i = 0; i < 3 * (p.head_sets > 1 ? p.head_sets + 1 : 1); i++) p.scratch[i] = take(p, mx * s);
     if (stack_has_norm(c, true) || stack_has_norm(c, false)) {
@@ -849,7 +849,7 @@ static int conv3x3(moge_handle* h, const T* in, const T* w, const float* bias, T
     g.pixW = Ww; g.pixH = Hh;
     if (uv) g.uv = *uv;
     if (fused) *fused = false;
-    if (side && std::is_same<T, f16>::value && Cin == Cout && moge_tune_get("CONV_PP", 1)) {
+    if (side && std::is_same<T, f16>::value && Cin == Cout && moge_tune_get(TK_CONV_PP)) {
         // fused 1x1 side input (x + in_l(neck_l), modules.py:245): only the halo kernel implements it; `bias` must already hold
         // the sum of both biases (the caller passes the combined vector when *fused comes back true, see below)
         GemmArgs g2 = g;
@@ -904,7 +904,7 @@ template <typename T>
 static int convT_conv3_fused(moge_handle* h, const T* in, const T* wc, const T* dw, const float* bias4, T* out, int B, int Hl, int Wl, int Cin, int Cout,
                              const UVTerm* uv, const T* side, const T* side_w, hipStream_t st, bool* done) {
     *done = false;
-    if (!std::is_same<T, f16>::value || !moge_tune_get("FUSE_CT3", 1) || !moge_tune_get("CONV_PP", 1)) return 0;
+    if (!std::is_same<T, f16>::value || !moge_tune_get(TK_FUSE_CT3) || !moge_tune_get(TK_CONV_PP)) return 0;
     GemmArgs g = gemm_args();
     g.a = in; g.H = Hl; g.W = Wl; g.C = Cin; g.w = wc; g.ldw = 4 * Cin;
     g.M = B * Hl * Wl; g.N = 4 * Cout; g.K = 4 * Cin;
@@ -968,7 +968,7 @@ static int res_blocks(moge_handle* h, const std::string& name, int l, int n, T* 
         // CONV_RB (default OFF): measured on MI355X the fused launch is 5-10 % SLOWER than the two conv_pp launches at the bench's level-3 shape
         // (1.44-1.46 vs 1.37-1.38 ms at batch 32, profiles/r03a_kbench_rb.log, timeline r03j: one 130 KiB workgroup per CU exposes every
         // latency the two-per-CU conv_pp form hides, and the MFMA segments run at 21.7 clocks per MFMA beside the partner's read segment)
-        if (std::is_same<T, f16>::value && Ch == C && moge_tune_get("CONV_RB", 0) && (may_swap || ((n - j) >= 2) || cur != x)) {
+        if (std::is_same<T, f16>::value && Ch == C && moge_tune_get(TK_CONV_RB) && (may_swap || ((n - j) >= 2) || cur != x)) {
             // (without may_swap the result must end in x: fuse blocks in pairs, or the last one when the data currently sits in tmp)
             GemmArgs g = gemm_args();
             g.a = cur; g.H = Hh; g.W = Ww; g.C = C; g.relu_in = 1; g.w = w1; g.ldw = 9 * C; g.M = B * Hh * Ww; g.N = C; g.K = 9 * C;
@@ -1203,7 +1203,7 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
     // l4dot: ... and with 64 -> 32 channels on phase resamplers, out_k(x4_k + in4_k(n4)) = Wout_k x4_k + (Wout_k Win4_k) n4 + b2_k is evaluated
     // INSIDE the two 64 -> 4 x 32 resampler convs (conv_pp.hip, fused output conv); head_final only resizes and remaps 4 + 4 floats per tap
     const bool l4dot = fuse_l4 && c.neck_res_blocks[MOGE_LEVELS - 1] == 0 && c.dims[4] == 32 && c.dims[3] == 64 && rs_is_phase(c.neck_resamplers[3]) &&
-                       rs_is_phase(c.head_resamplers[3]) && moge_tune_get("CONV_PP", 1) != 0;
+                       rs_is_phase(c.head_resamplers[3]) && moge_tune_get(TK_CONV_PP) != 0;
     CHK(encode<T>(h, image, img_dtype, pl.H, pl.W, pl, st, !compose));
     // (the scale head runs behind the heads, see below)
     int nheads = 0;
@@ -1212,7 +1212,7 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
     // launches on ONE stream.  HEAD_PIPE (default, round 6): every head on a side stream, level l of a head released by the event of neck level l;
     // HEAD_PIPE 0 (rounds 3-5): the first head on the caller's stream, the others forked behind the whole neck
     const bool par_heads = pl.head_sets > 1 && !h->prof_on;
-    const bool pipe = par_heads && moge_tune_get("HEAD_PIPE", 1) != 0;
+    const bool pipe = par_heads && moge_tune_get(TK_HEAD_PIPE) != 0;
     auto neck_level_done = [&](int l) -> int {
         if (!pipe) return 0;
         if (!h->ev_lvl[pl.slot][l]) HIPCHK(hipEventCreateWithFlags(&h->ev_lvl[pl.slot][l], hipEventDisableTiming));
@@ -1340,7 +1340,7 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
                 const float* plain_bias = M(h, name + S(".resamplers.%d.%s.bias", l - 1, rs_final_conv(rsl)));
                 // resampler conv, with the head's `x + in_l(neck_l)` fused as a 1x1 side input when the halo kernel takes the shape
                 // (the first attempt passes the combined bias; if the shape is not eligible nothing ran and the plain form follows)
-                const bool try_fuse = fuse_in && rsl == MOGE_RS_CONV_TRANSPOSE && moge_tune_get("CONV_PP", 1) != 0 && !(l == MOGE_LEVELS - 1 && fuse_l4);
+                const bool try_fuse = fuse_in && rsl == MOGE_RS_CONV_TRANSPOSE && moge_tune_get(TK_CONV_PP) != 0 && !(l == MOGE_LEVELS - 1 && fuse_l4);
                 if (try_fuse) {
                     GemmArgs probe = gemm_args();
                     probe.a = Sc[a]; probe.H = Hh; probe.W = Ww; probe.C = co; probe.w = P<T>(h, name + S(".rs%d.w3", l - 1)); probe.ldw = 9 * co;
@@ -2021,7 +2021,7 @@ static int check_call(moge_handle* h, const void* image, int B, int H, int W, in
 static constexpr int BATCH_SPLIT_MIN_PART = 3;
 static int split_parts(moge_handle* h, int B) {
     if (h->prof_on) return 1;
-    int n = moge_tune_get("BATCH_SPLIT", 2);
+    int n = moge_tune_get(TK_BATCH_SPLIT);
     if (n > moge_handle::MAX_SPLIT) n = moge_handle::MAX_SPLIT;
     while (n > 1 && B / n < BATCH_SPLIT_MIN_PART) n--;
     return n < 2 ? 1 : n;

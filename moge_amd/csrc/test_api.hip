@@ -150,7 +150,7 @@ static int t_attention(const float* q, const float* k, const float* v, float* o,
         const size_t awb = attention_pp_ws_bytes(B, nh, N);
         if (awb) { TCHK(aws.alloc(awb)); TCHK(hipMemsetAsync(aws.p, 0, attention_pp_ws_counter_bytes(B, nh, N), st)); }
         TL(launch_attention_pp(qb.p, kb.p, vr.p, ob.p, B, nh, N, st, awb ? aws.p : nullptr, awb));
-        if (awb && moge_tune_get("ATTN_SK_TWICE", 0)) TL(launch_attention_pp(qb.p, kb.p, vr.p, ob.p, B, nh, N, st, aws.p, awb));      // tests: the counters are left zero
+        if (awb && moge_tune_get(TK_ATTN_SK_TWICE)) TL(launch_attention_pp(qb.p, kb.p, vr.p, ob.p, B, nh, N, st, aws.p, awb));      // tests: the counters are left zero
     } else {
         TL(launch_attention<T>(qb.p, kb.p, vb.p, ob.p, B, nh, N, Npad, st));
     }

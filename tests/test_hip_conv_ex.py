@@ -74,11 +74,8 @@ def test_conv_fused_side_input(H, side_reg, B, Hh, Ww, Cin, Cout):
     side = r16(torch.randn(B, Hh, Ww, Cin, generator=g))
     sw = r16(torch.randn(Cout, Cin, generator=g) / Cin ** 0.5)
     ref = conv_ref(x, w, b) + torch.einsum("bhwc,oc->bhwo", side.cuda(), sw.cuda())
-    L.tune("CONV_SIDE_REG", side_reg)
-    try:
+    with L.tuned(CONV_SIDE_REG=side_reg):
         out = H.conv_ex(x, w, b, side=side, side_w=sw)
-    finally:
-        L.tune("CONV_SIDE_REG", 1)
     close(out, ref, "side")
 
 
@@ -176,11 +173,8 @@ def test_fused_residual_block_equals_two_launch_path_bitwise(X, grid):
     two = X.conv_ex(h, w2, b2, add=x)
     outs = []
     for cap in (grid, 1 << 20):
-        L.tune("CONV_GRID", cap)
-        try:
+        with L.tuned(CONV_GRID=cap):
             outs.append(X.conv_ex(x, w1, b1, w2=w2, bias2=b2))
-        finally:
-            L.tune("CONV_GRID", 0)
     assert torch.equal(outs[0], outs[1])
     assert torch.equal(outs[0], two)
 

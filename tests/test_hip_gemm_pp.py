@@ -2,7 +2,7 @@
 PyTorch fp32 reference of the same op, and bit-for-bit against the latency-regime kernels of gemm.hip.
 
 Dispatch (gemm.hip launch_gemm): a GEMM goes to the ping-pong kernel when N % 256 == 0, K % 64 == 0 and it has at least PP_MIN_TILES
-(96) tiles of 256x256; everything smaller runs gemm_glds_kernel / gemm_kernel.  The tests pin the kernel under test explicitly:
+tiles of 256x256; everything smaller runs gemm_glds_kernel / gemm_kernel.  The tests pin the kernel under test explicitly:
   force = "pp"      moge_tune_set("PP_MIN_TILES", 0)   -> the ping-pong kernel for every eligible shape; PP_KERN picks which of the two
                     product kernels (gemm_pp128p_kernel: persistent, the default; gemm_pp128m16_kernel: one tile per workgroup) - each test runs both
   force = "latency" moge_tune_set("GEMM_PP", 0)        -> gemm.hip only
@@ -36,29 +36,15 @@ def kern(request):
     return request.param
 
 
-class Force:
-    """Pin the GEMM dispatch for the duration of a block, then restore the production defaults."""
-
-    def __init__(self, mode, kern=-1):
-        self.mode, self.kern = mode, kern
-
-    def __enter__(self):
-        from moge_amd import _lib as L
-        if self.mode == "pp":
-            L.tune("PP_MIN_TILES", 0)
-            L.tune("PP_KERN", self.kern)
-            if self.kern >= 2:
-                L.tune("PP_GRID", 24)      # persistent kernel: 3 workgroups per XCD, so even the small shapes walk several tiles each
-        elif self.mode == "latency":
-            L.tune("GEMM_PP", 0)
-        return self
-
-    def __exit__(self, *exc):
-        from moge_amd import _lib as L
-        L.tune("PP_MIN_TILES", 96)
-        L.tune("GEMM_PP", 1)
-        L.tune("PP_KERN", -1)
-        L.tune("PP_GRID", 0)
+def Force(mode, kern=None):
+    """Pin the GEMM dispatch for the duration of a `with` block (moge_amd._lib.tuned resets the keys on the way out)."""
+    from moge_amd import _lib as L
+    if mode == "latency":
+        return L.tuned(GEMM_PP=0)
+    assert mode == "pp" and kern is not None, "Force('pp', kern): name the throughput kernel"
+    if kern >= 2:
+        return L.tuned(PP_MIN_TILES=0, PP_KERN=kern, PP_GRID=24)      # persistent kernel: 3 workgroups per XCD, so even the small shapes walk several tiles each
+    return L.tuned(PP_MIN_TILES=0, PP_KERN=kern)
 
 
 def h16(t):
@@ -319,13 +305,9 @@ def test_latency_kernel_ring_depths_are_bit_identical(H, M, N, K):
     A, W, b = rnd(M, K, seed=21), rnd(N, K, seed=22, scale=K ** -0.5), rnd(N, seed=23)
     gamma, x0 = rnd(N, seed=24), rnd(M, N, seed=25, scale=3.0)
     outs = {}
-    try:
-        for ns in (2, 3, 4):
-            L.tune("GLDS_SMALL_NS", ns)
-            with Force("latency"):
-                outs[ns] = (H.gemm_ex(H.TG_STORE, A, W, b, act=2)["out"], H.gemm_ex(H.TG_RESID, A, W, b, xres=x0, gamma=gamma, want_x16=True))
-    finally:
-        L.tune("GLDS_SMALL_NS", 3)
+    for ns in (2, 3, 4):
+        with L.tuned(GLDS_SMALL_NS=ns, GEMM_PP=0):
+            outs[ns] = (H.gemm_ex(H.TG_STORE, A, W, b, act=2)["out"], H.gemm_ex(H.TG_RESID, A, W, b, xres=x0, gamma=gamma, want_x16=True))
     close(outs[3][0], h16(F.gelu(acc_ref(A, W) + b)), what="gelu store")
     close(outs[3][1]["xres"], x0 + gamma * (acc_ref(A, W) + b), tol=2e-6, what="resid x")
     for ns in (2, 4):

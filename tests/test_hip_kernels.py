@@ -85,11 +85,8 @@ def test_attention_64_queries_per_wave_is_bit_identical(H, B, nh, N):
     ref = F.scaled_dot_product_attention(q.cuda(), k.cuda(), v.cuda()).permute(0, 2, 1, 3).reshape(B, N, nh * 64)
     outs = {}
     for kern in (1, 2):
-        L.tune("ATTN_KERN", kern)
-        try:
+        with L.tuned(ATTN_KERN=kern):
             outs[kern] = H.attention(1, q, k, v)
-        finally:
-            L.tune("ATTN_KERN", 3)
         assert relmax(outs[kern], ref) < 1e-2, kern
     assert torch.equal(outs[1], outs[2])
 
@@ -114,13 +111,8 @@ def test_attention_ping_pong_kernel_is_bit_identical(X, B, nh, N, prio):
     ref = F.scaled_dot_product_attention(q.cuda(), k.cuda(), v.cuda()).permute(0, 2, 1, 3).reshape(B, N, nh * 64)
     outs = {}
     for kern in (1, 4):
-        L.tune("ATTN_KERN", kern)
-        L.tune("ATTN_X_PRIO", prio)
-        try:
+        with L.tuned(ATTN_KERN=kern, ATTN_X_PRIO=prio):
             outs[kern] = X.attention(1, q, k, v)
-        finally:
-            L.tune("ATTN_KERN", 3)
-            L.tune("ATTN_X_PRIO", 0)
         assert relmax(outs[kern], ref) < 1e-2, kern
     assert torch.equal(outs[1], outs[4])
 
@@ -146,17 +138,14 @@ def test_attention_stream_k(X, B, nh, N, wgs, qb):
         k[:, :, N // 2 + 3] = q[:, :, 5] * 6.0
         k[:, 0, N - 2] = q[:, 0, min(70, N - 1)] * 5.0
     ref = F.scaled_dot_product_attention(q.cuda(), k.cuda(), v.cuda()).permute(0, 2, 1, 3).reshape(B, N, nh * 64)
-    L.tune("ATTN_SK", 0)
-    try:
+    with L.tuned(ATTN_SK=0):
         plain = X.attention(1, q, k, v)
-        L.tune("ATTN_SK", 2); L.tune("ATTN_SK_QB", qb); L.tune("ATTN_SK_WGS", wgs); L.tune("ATTN_SK_MIN_TILES", 1 if wgs == 0 and N < 2000 else 12)
+    short = {"ATTN_SK_MIN_TILES": 1} if wgs == 0 and N < 2000 else {}       # (else the table's: a segment shorter than that is mostly prologue)
+    with L.tuned(ATTN_SK=2, ATTN_SK_QB=qb, ATTN_SK_WGS=wgs, **short):
         a = X.attention(1, q, k, v)
         b = X.attention(1, q, k, v)
-        L.tune("ATTN_SK_TWICE", 1)
-        c = X.attention(1, q, k, v)
-    finally:
-        for key, dflt in (("ATTN_SK", 0), ("ATTN_SK_QB", 2), ("ATTN_SK_WGS", 0), ("ATTN_SK_MIN_TILES", 12), ("ATTN_SK_TWICE", 0)):
-            L.tune(key, dflt)
+        with L.tuned(ATTN_SK_TWICE=1):
+            c = X.attention(1, q, k, v)
     assert relmax(a, ref) < 1e-2
     assert relmax(a, plain) < 2e-3
     assert torch.equal(a, b) and torch.equal(a, c)
@@ -182,14 +171,11 @@ def test_attention_key_split_inside_the_workgroup(H, B, nh, N, ks):
         k[:, 0, N - 2] = q[:, 0, min(70, N - 1)] * 5.0      # second half, the masked last tile
         k[:, :, (3 * N) // 4] = q[:, :, N - 1] * 6.0        # second half, seen by the last query (a tail wave)
     ref = F.scaled_dot_product_attention(q.cuda(), k.cuda(), v.cuda()).permute(0, 2, 1, 3).reshape(B, N, nh * 64)
-    try:
-        L.tune("ATTN_KS", 0)
+    with L.tuned(ATTN_KS=0):
         plain = H.attention(1, q, k, v)
-        L.tune("ATTN_KS", ks)
+    with L.tuned(ATTN_KS=ks):
         a = H.attention(1, q, k, v)
         b = H.attention(1, q, k, v)
-    finally:
-        L.tune("ATTN_KS", 1)
     assert relmax(a, ref) < 1e-2
     assert relmax(a, plain) < 2e-3
     assert torch.equal(a, b)
@@ -197,15 +183,53 @@ def test_attention_key_split_inside_the_workgroup(H, B, nh, N, ks):
     # (no overflow guard trips that raise the max in one key range and not in the other) the two forms differ by fp32 summation order only - a handful of last-bit
     # differences after the fp16 rounding (observed 0.03-0.15 % of the values, rms 1e-6)
     q2, k2, v2 = (torch.randn(B, nh, N, 64, generator=g) for _ in range(3))
-    try:
-        L.tune("ATTN_KS", 0)
+    with L.tuned(ATTN_KS=0):
         plain2 = H.attention(1, q2, k2, v2)
-        L.tune("ATTN_KS", ks)
+    with L.tuned(ATTN_KS=ks):
         a2 = H.attention(1, q2, k2, v2)
-    finally:
-        L.tune("ATTN_KS", 1)
     assert (a2 != plain2).float().mean().item() < 5e-3
     assert relmax(a2, plain2) < 1e-3
+
+
+_OVERRIDE_CHILD = r"""
+import sys, torch
+from moge_amd import _lib as L
+from tests import hip_util as H
+q, k, v = torch.load(sys.argv[1])
+out = {"ks": [L.tune_value("ATTN_KS")]}
+out["before"] = H.attention(1, q, k, v).cpu()
+with L.tuned(ATTN_KS=0):
+    out["ks"].append(L.tune_value("ATTN_KS"))
+    out["inside"] = H.attention(1, q, k, v).cpu()
+out["ks"].append(L.tune_value("ATTN_KS"))
+out["after"] = H.attention(1, q, k, v).cpu()
+torch.save(out, sys.argv[2])
+"""
+
+
+def test_environment_override_survives_a_tuned_block(H, tmp_path):
+    """A process started under MOGE_ATTN_KS=2 (how tools/gpu_call.sh runs the suite under another kernel) computes with that kernel before AND after a
+    `with L.tuned(ATTN_KS=0)` block - bit-identical results, the block's exit goes back to the environment's value and not to the table's default - and inside
+    the block computes what this process computes under the same block."""
+    import subprocess
+    import sys
+    from moge_amd import _lib as L
+    B, nh, N = 1, 2, 300
+    g = torch.Generator().manual_seed(N + 3)
+    q, k, v = (torch.randn(B, nh, N, 64, generator=g) for _ in range(3))
+    torch.save((q, k, v), tmp_path / "qkv.pt")
+    with L.tuned(ATTN_KS=0):
+        mine = H.attention(1, q, k, v).cpu()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {**{key: val for key, val in os.environ.items() if not key.startswith("MOGE_")}, "MOGE_ATTN_KS": "2"}
+    r = subprocess.run([sys.executable, "-c", _OVERRIDE_CHILD, str(tmp_path / "qkv.pt"), str(tmp_path / "out.pt")], capture_output=True, text=True, env=env, cwd=root,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = torch.load(tmp_path / "out.pt")
+    assert out["ks"] == [2, 0, 2]
+    assert torch.equal(out["before"], out["after"])
+    assert not torch.equal(out["before"], out["inside"])           # the override does select another kernel: the forced key split sums in another order
+    assert torch.equal(out["inside"], mine)
 
 
 def test_attention_online_softmax_rescale(H):
@@ -249,11 +273,8 @@ def test_conv3x3_persistent_walks_tiles(H, grid, B, Hh, Ww, Cin, Cout, relu):
     b = torch.randn(Cout, generator=g)
     outs = []
     for cap in (grid, 1 << 20):
-        L.tune("CONV_GRID", cap)
-        try:
+        with L.tuned(CONV_GRID=cap):
             outs.append(H.conv3x3(1, x, w, b, relu_in=relu))
-        finally:
-            L.tune("CONV_GRID", 0)
     assert torch.equal(outs[0], outs[1])
     xin = F.relu(x) if relu else x
     ref = F.conv2d(F.pad(xin.permute(0, 3, 1, 2).cuda(), (1, 1, 1, 1), mode="replicate"), w.cuda(), b.cuda()).permute(0, 2, 3, 1)

@@ -68,19 +68,16 @@ def test_batches_above_32_equal_their_single_image_results(MoGeModel, tmp_path_f
     x = torch.rand(B, 3, 518, 518, generator=torch.Generator().manual_seed(7))
     try:
         model.half()
-        L.tune("BATCH_SPLIT", split)
-        batch = model.infer(x)
-        L.tune("BATCH_SPLIT", 2)
+        with L.tuned(BATCH_SPLIT=split):
+            batch = model.infer(x)
         for k in ("points", "depth"):
             assert batch[k].shape[0] == B
-        L.tune("ATTN_KS", 0)         # the batch-invariant form of the one-image attention (the default splits a single image's key range inside the workgroup: within the band, tests/test_hip_parity.py)
-        for i in (0, B // 2 - 1, B // 2, B - 1):
-            single = model.infer(x[i])
-            for k in single:
-                _same(batch[k][i], single[k], f"{k}: item {i} of the batch of {B} differs from its single-image result")
+        with L.tuned(ATTN_KS=0):     # the batch-invariant form of the one-image attention (the default splits a single image's key range inside the workgroup: within the band, tests/test_hip_parity.py)
+            for i in (0, B // 2 - 1, B // 2, B - 1):
+                single = model.infer(x[i])
+                for k in single:
+                    _same(batch[k][i], single[k], f"{k}: item {i} of the batch of {B} differs from its single-image result")
     finally:
-        L.tune("BATCH_SPLIT", 2)
-        L.tune("ATTN_KS", 1)
         model.float()
         torch.cuda.empty_cache()
 

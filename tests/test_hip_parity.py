@@ -127,16 +127,13 @@ def test_fp16_throughput_kernels_in_the_model_match_reference_golden(MoGeModel, 
     band, g = fp16_band(meta, gold, "half"), golden_infer(gold)
     try:
         model.half()
-        L.tune("ATTN_KS", 0)        # (a single image's attention otherwise splits its key range inside the workgroup: within the band, not bit-identical to a batch item - test_single_image_key_split_attention_...)
-        base = model.infer(x, **kw)
-        L.tune("PP_MIN_TILES", 0)
-        forced = model.infer(x, **kw)
-        L.tune("PP_MIN_TILES", 96)
-        xb = x.expand(9, *x.shape[1:]).contiguous()        # 9 x 3601 rows = 127 row tiles x >= 3 column tiles: ping-pong regime, two half-batch streams
-        batch = model.infer(xb, **kw)
+        with L.tuned(ATTN_KS=0):    # (a single image's attention otherwise splits its key range inside the workgroup: within the band, not bit-identical to a batch item - test_single_image_key_split_attention_...)
+            base = model.infer(x, **kw)
+            with L.tuned(PP_MIN_TILES=0):
+                forced = model.infer(x, **kw)
+            xb = x.expand(9, *x.shape[1:]).contiguous()        # 9 x 3601 rows = 127 row tiles x >= 3 column tiles: ping-pong regime, two half-batch streams
+            batch = model.infer(xb, **kw)
     finally:
-        L.tune("PP_MIN_TILES", 96)
-        L.tune("ATTN_KS", 1)
         model.float()
     check_fp16(sub(forced, st), g, band)
     for k in base:
@@ -175,13 +172,12 @@ def test_bench_batch_of_32_distinct_images_matches_its_single_image_results(MoGe
             again = model.infer(x)
             for k in batch:
                 _same(again[k], batch[k], f"{k}: run {rep + 2} of the same batch differs from run 1 (a race)")
-        L.tune("ATTN_KS", 0)         # the batch-invariant form of the one-image attention (the default splits a single image's key range inside the workgroup)
-        for i in (0, 15, 16, 31):
-            single = model.infer(x[i])
-            for k in single:
-                _same(batch[k][i], single[k], f"{k}: item {i} of the batch of 32 differs from its single-image result")
+        with L.tuned(ATTN_KS=0):     # the batch-invariant form of the one-image attention (the default splits a single image's key range inside the workgroup)
+            for i in (0, 15, 16, 31):
+                single = model.infer(x[i])
+                for k in single:
+                    _same(batch[k][i], single[k], f"{k}: item {i} of the batch of 32 differs from its single-image result")
     finally:
-        L.tune("ATTN_KS", 1)
         model.float()
     check_fp16(sub({k: v[:1] for k, v in batch.items()}, case.get("stride", 1)), golden_infer(gold), fp16_band(meta, gold, "half"))
 
@@ -268,11 +264,8 @@ def test_properties_at_baseline_size(MoGeModel, tmp_path_factory):
     for k in out:
         assert torch.equal(out[k], out2[k]), f"{k} not deterministic"
     from moge_amd import _lib as L
-    L.tune("ATTN_KS", 0)             # the batch-invariant form of the one-image attention
-    try:
+    with L.tuned(ATTN_KS=0):         # the batch-invariant form of the one-image attention
         single = model.infer(x[1])
-    finally:
-        L.tune("ATTN_KS", 1)
     for k in out:
         a, b = out[k][1], single[k]
         if a.dtype == torch.bool:
@@ -301,9 +294,8 @@ def test_batch_split_streams_are_bit_identical(MoGeModel, tmp_path_factory):
                 model.half()
             for B in (9, 6, 7):                     # 4 + 5, 3 + 3 (the smallest parts split_parts allows), 3 + 4
                 x = torch.rand(B, 3, 84, 112, generator=torch.Generator().manual_seed(3 + B))
-                L.tune("BATCH_SPLIT", 0)
-                ref = model.infer(x, num_tokens=108)
-                L.tune("BATCH_SPLIT", 2)
+                with L.tuned(BATCH_SPLIT=0):
+                    ref = model.infer(x, num_tokens=108)
                 out = model.infer(x, num_tokens=108)
                 for k in ref:
                     a, b = out[k], ref[k]
@@ -313,7 +305,6 @@ def test_batch_split_streams_are_bit_identical(MoGeModel, tmp_path_factory):
                         fin = torch.isfinite(b)
                         assert torch.equal(fin, torch.isfinite(a)) and torch.equal(a[fin], b[fin]), f"{k}: split != single stream (B={B})"
     finally:
-        L.tune("BATCH_SPLIT", 2)
         model.float()
 
 
@@ -330,12 +321,10 @@ def test_fused_resamplers_change_the_fp16_result_by_less_than_the_band(MoGeModel
     band = fp16_band(meta, gold, "half")
     try:
         model.half()
-        L.tune("FUSE_CT3", 0)
-        pair = sub(model.infer(x), st)
-        L.tune("FUSE_CT3", 1)
+        with L.tuned(FUSE_CT3=0):
+            pair = sub(model.infer(x), st)
         fused = sub(model.infer(x), st)
     finally:
-        L.tune("FUSE_CT3", 1)
         model.float()
     assert not np.array_equal(pair["points"], fused["points"]), "FUSE_CT3 changed nothing: the fused resamplers are not being used"
     check_fp16(pair, golden_infer(gold), band)
@@ -360,13 +349,11 @@ def test_single_image_key_split_attention_stays_within_half_a_band(MoGeModel, tm
     band = fp16_band(meta, gold, "half")
     try:
         model.half()
-        L.tune("ATTN_KS", 0)
-        plain = sub(model.infer(x), st)
-        L.tune("ATTN_KS", 1)
+        with L.tuned(ATTN_KS=0):
+            plain = sub(model.infer(x), st)
         split = sub(model.infer(x), st)
         again = sub(model.infer(x), st)
     finally:
-        L.tune("ATTN_KS", 1)
         model.float()
     assert not np.array_equal(plain["points"], split["points"]), "ATTN_KS changed nothing: the key-split attention is not being used"
     for k in split:
@@ -388,36 +375,32 @@ def test_head_streams_are_bit_identical(MoGeModel, tmp_path_factory):
     from moge_amd import _lib as L
     model, cfg, sd = get_model(MoGeModel, "tiny-vits-normal", 0, True, tmp_path_factory)
     try:
-        L.tune("HEAD_STREAMS_MAX_B", 16)
-        for B in (1, 3, 9):
-            x = torch.rand(B, 3, 84, 112, generator=torch.Generator().manual_seed(11 + B))
-            for half in (False, True):
-                model.half() if half else model.float()
-                L.tune("HEAD_STREAMS", 0)
-                ref = model.infer(x, num_tokens=108)
-                L.tune("HEAD_STREAMS", 1)
-                for pipe in (0, 1, 1):                  # HEAD_PIPE 1 (default): every head on a side stream, released level by level behind the neck; 0: forked behind the whole neck.
-                    L.tune("HEAD_PIPE", pipe)           # (twice: the second call reuses streams, events and scratch of the first)
-                    for _ in range(2):
-                        out = model.infer(x, num_tokens=108)
-                        for k in ref:
-                            _same(out[k], ref[k], f"{k}: head streams != one stream (B={B}, half={half}, HEAD_PIPE={pipe})")
-        # a subset of the outputs (forward with only normal + mask requested: head 0 is skipped, the first REQUESTED head is not head index 0)
-        model.float()
-        x = torch.rand(2, 3, 84, 112, generator=torch.Generator().manual_seed(5)).cuda()
-        full = model.forward(x, 108)
-        for hs, pipe in ((0, 1), (1, 0), (1, 1)):
-            L.tune("HEAD_STREAMS", hs); L.tune("HEAD_PIPE", pipe)
-            o = L.Outputs()
-            nrm = torch.empty_like(full["normal"]); mp = torch.empty_like(full["mask"])
-            o.normal, o.mask_prob = nrm.data_ptr(), mp.data_ptr()
-            L.check(L.lib.moge_forward(model._handle, x.data_ptr(), 0, 2, 84, 112, 9, 12, C.byref(o), L.stream_ptr()))
-            torch.cuda.synchronize()
-            assert torch.equal(nrm, full["normal"]) and torch.equal(mp, full["mask"]), f"subset of outputs, HEAD_STREAMS={hs}, HEAD_PIPE={pipe}"
+        with L.tuned(HEAD_STREAMS_MAX_B=16):
+            for B in (1, 3, 9):
+                x = torch.rand(B, 3, 84, 112, generator=torch.Generator().manual_seed(11 + B))
+                for half in (False, True):
+                    model.half() if half else model.float()
+                    with L.tuned(HEAD_STREAMS=0):
+                        ref = model.infer(x, num_tokens=108)
+                    for pipe in (0, 1, 1):                  # HEAD_PIPE 1 (default): every head on a side stream, released level by level behind the neck; 0: forked behind the whole neck.
+                        with L.tuned(HEAD_STREAMS=1, HEAD_PIPE=pipe):      # (twice: the second call reuses streams, events and scratch of the first)
+                            for _ in range(2):
+                                out = model.infer(x, num_tokens=108)
+                                for k in ref:
+                                    _same(out[k], ref[k], f"{k}: head streams != one stream (B={B}, half={half}, HEAD_PIPE={pipe})")
+            # a subset of the outputs (forward with only normal + mask requested: head 0 is skipped, the first REQUESTED head is not head index 0)
+            model.float()
+            x = torch.rand(2, 3, 84, 112, generator=torch.Generator().manual_seed(5)).cuda()
+            full = model.forward(x, 108)
+            for hs, pipe in ((0, 1), (1, 0), (1, 1)):
+                with L.tuned(HEAD_STREAMS=hs, HEAD_PIPE=pipe):
+                    o = L.Outputs()
+                    nrm = torch.empty_like(full["normal"]); mp = torch.empty_like(full["mask"])
+                    o.normal, o.mask_prob = nrm.data_ptr(), mp.data_ptr()
+                    L.check(L.lib.moge_forward(model._handle, x.data_ptr(), 0, 2, 84, 112, 9, 12, C.byref(o), L.stream_ptr()))
+                    torch.cuda.synchronize()
+                    assert torch.equal(nrm, full["normal"]) and torch.equal(mp, full["mask"]), f"subset of outputs, HEAD_STREAMS={hs}, HEAD_PIPE={pipe}"
     finally:
-        L.tune("HEAD_STREAMS", 1)
-        L.tune("HEAD_PIPE", 1)
-        L.tune("HEAD_STREAMS_MAX_B", 1)
         model.float()
 
 

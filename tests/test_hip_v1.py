@@ -101,11 +101,10 @@ def test_v1_fp16_forward_noise_against_the_reference_redraws(name, tmp_path_fact
     try:
         model.half()
         for ks, mid in ((0, 0), (1, 0), (1, 9), (1, 25)):
-            L.tune("ATTN_KS", ks); L.tune("ATTN_KS_MID", mid)
-            f = model.forward(xb, nt)["points"].float().cpu().numpy()[:, ::st, ::st].astype(np.float64)
+            with L.tuned(ATTN_KS=ks, ATTN_KS_MID=mid):
+                f = model.forward(xb, nt)["points"].float().cpu().numpy()[:, ::st, ::st].astype(np.float64)
             seen.append(float(np.abs(f - gf).mean() / np.abs(gf).mean()))
     finally:
-        L.tune("ATTN_KS", 1); L.tune("ATTN_KS_MID", 0)
         model.float()
     print(f"[gate v1 fp16 half forward] {name}: library " + " / ".join(f"{v:.2e}" for v in seen) + f" reference {min(ref_noise):.2e} ... {max(ref_noise):.2e}")
     assert max(seen) <= FP16_FACTOR * float(np.median(ref_noise)), (seen, ref_noise)

@@ -11,7 +11,7 @@ for scale in (1.0, 3.0, 8.0):
     k = k + torch.linspace(0, 2.0, N)[None, None, :, None] * q.mean(dim=2, keepdim=True) / q.mean(dim=2, keepdim=True).norm(dim=-1, keepdim=True)
     ref = F.scaled_dot_product_attention(q.double().cuda(), k.double().cuda(), v.double().cuda()).permute(0, 2, 1, 3).reshape(B, N, nh * 64)
     for kern in (0, 1):
-        L.tune("ATTN_KERN", kern)
-        o = H.attention(1, q, k, v).double()
+        with L.tuned(ATTN_KERN=kern):
+            o = H.attention(1, q, k, v).double()
         e = (o - ref).abs()
         print(f"scale {scale} kern {kern}: max {float(e.max()):.3e} mean {float(e.mean()):.3e} p999 {float(torch.quantile(e.flatten()[:4000000].float(), 0.999)):.3e} refmax {float(ref.abs().max()):.2f}")

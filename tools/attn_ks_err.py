@@ -18,10 +18,8 @@ for (B, nh, N, sink) in [(1, 16, 1370, 0.0), (1, 16, 1370, 8.0), (1, 16, 3601, 0
         refh = F.scaled_dot_product_attention(qh, kh, vh).permute(0, 2, 1, 3).reshape(B, N, nh * 64)
         res = {}
         for ks in (0, 1, 2, 4):
-            L.tune("ATTN_KS", ks)
-            o = H.attention(1, q, k, v).double()
-            res[ks] = o
-        L.tune("ATTN_KS", 1)
+            with L.tuned(ATTN_KS=ks):
+                res[ks] = H.attention(1, q, k, v).double()
         line = f"B{B} nh{nh} N{N} sink{sink} seed{seed}:"
         for ks, o in res.items():
             e = (o - refh)

@@ -140,20 +140,22 @@ __global__ __launch_bounds__(256, QB > 2 ? 2 : 3) void attn_pp16sk_kernel(const 
 // The stream-K form's workspace: 2 slots per workgroup + one counter per query block (counters first; the caller zeroes them ONCE - the kernel leaves them zero).
 // Returns 0 when the shape does not take that path (launch_attention_pp then ignores the workspace).
 static int attn_sk_plan(int B, int nh, int Ntok, int* qb_out, int* nx_out, int* gx_out) {
-    const int sk = moge_tune_get("ATTN_SK", 0);                       // 0 off (default: it is slower), 1 by grid size, 2 always (tests)
-    if (!sk || moge_tune_get("ATTN_KERN", AP_KERN_DEFAULT) != 3) return 0;
+    const int sk = moge_tune_get(TK_ATTN_SK);                       // 0 off (default: it is slower), 1 by grid size, 2 always (tests)
+    if (!sk || moge_tune_get(TK_ATTN_KERN) != 3) return 0;
     const int cus = pp_device_cus();
     const long wgs2 = (long)((Ntok + 127) / 128) * B * nh;
-    if (sk == 1 && wgs2 > moge_tune_get("ATTN_SK_MAX_WGS", 3 * cus)) return 0;       // (the same line that selects QB = 2: a grid of one round or less)
-    const int QB = moge_tune_get("ATTN_SK_QB", 2) == 4 ? 4 : 2;
+    int sk_max = moge_tune_get(TK_ATTN_SK_MAX_WGS);
+    if (sk_max < 0) sk_max = 3 * cus;                                 // (the table's default)
+    if (sk == 1 && wgs2 > sk_max) return 0;                           // (the same line that selects QB = 2: a grid of one round or less)
+    const int QB = moge_tune_get(TK_ATTN_SK_QB) == 4 ? 4 : 2;
     const int ntiles = (Ntok + 63) >> 6, QBK = (Ntok + 64 * QB - 1) / (64 * QB);
     const int nx = ((B * nh) & 7) == 0 ? 8 : 1;
     const long U = (long)(B * nh / nx) * QBK * ntiles;
     const int slots_x = cus * (QB > 2 ? 2 : 3) / nx;                  // resident workgroups per range
-    const int min_tiles = moge_tune_get("ATTN_SK_MIN_TILES", 12);     // a segment shorter than this is mostly prologue
+    const int min_tiles = moge_tune_get(TK_ATTN_SK_MIN_TILES);     // a segment shorter than this is mostly prologue
     long gx = U / (min_tiles > 0 ? min_tiles : 1);
     gx = gx < 1 ? 1 : (gx > slots_x ? slots_x : gx);
-    if (const int f = moge_tune_get("ATTN_SK_WGS", 0)) gx = f;        // tests: any partition
+    if (const int f = moge_tune_get(TK_ATTN_SK_WGS)) gx = f;        // tests: any partition
     if (gx > U) gx = U;
     if (sk == 1 && gx * nx <= (long)((Ntok + 64 * QB - 1) / (64 * QB)) * B * nh) return 0;       // no more workgroups than the plain grid has: nothing to balance
     *qb_out = QB; *nx_out = nx; *gx_out = (int)gx;

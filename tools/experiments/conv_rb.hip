@@ -386,7 +386,7 @@ static int launch_conv_rb_var(const GemmArgs& g, hipStream_t st) {
     const long B = (long)g.M / ((long)g.H * g.W);
     const long tiles = B * ((g.H + 15) / 16) * ((g.W + 15) / 16);
     long slots = pp_device_cus();
-    const long cap = moge_tune_get("CONV_GRID", 0);      // tests: a small grid makes small problems walk many tiles per workgroup
+    const long cap = moge_tune_get(TK_CONV_GRID);      // tests: a small grid makes small problems walk many tiles per workgroup
     if (cap > 0) slots = cap;
     const long grid = tiles < slots ? tiles : slots;
     hipLaunchKernelGGL(conv_rb_kernel<VAR>, dim3((unsigned)grid), dim3(512), RB_SMEM, st, g);
@@ -395,7 +395,7 @@ static int launch_conv_rb_var(const GemmArgs& g, hipStream_t st) {
 
 int launch_conv_rb(const GemmArgs& g, hipStream_t st) {
     if (!conv_rb_eligible(g)) return -1;
-    switch (moge_tune_get("CONV_RB_VAR", 0)) {
+    switch (moge_tune_get(TK_CONV_RB_VAR)) {
     case 1: return launch_conv_rb_var<1>(g, st);
     case 2: return launch_conv_rb_var<2>(g, st);
     case 3: return launch_conv_rb_var<3>(g, st);

@@ -2,7 +2,7 @@
 //   kbench gemm [filter]     time launch_gemm<f16> variants on the hot-path shapes and check sampled rows against a
 //                            naive fp32 device reference
 //   kbench attn              time / check the attention kernels
-// Variants are selected through moge_tune_set() (same switches as the MOGE_* environment variables).
+// Variants are selected through moge_tune_set() (same switches as the MOGE_* environment variables) and left through moge_tune_reset().
 #include "../moge_amd/csrc/launchers.h"
 #include <cstdio>
 #include <cstdlib>
@@ -11,7 +11,10 @@
 #include <vector>
 #include <cmath>
 
-extern "C" void moge_tune_set(const char* key, int value);
+// a switch for the launches that follow / back to what the process started with.  A key the library does not have ends the run.
+static void tune_check(int rc) { if (rc) { fprintf(stderr, "kbench: %s\n", moge_last_error()); exit(2); } }
+static void tune(const char* key, int value) { tune_check(moge_tune_set(key, value)); }
+static void tune_reset(const char* key) { tune_check(moge_tune_reset(key)); }
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %s at %s:%d: %s\n", #x, __FILE__, __LINE__, hipGetErrorString(e_)); exit(2); } } while (0)
 
@@ -173,11 +176,15 @@ static int bench_gemm(const char* filter, int iters) {
     };
     // kern: PP_KERN (0 = gemm_pp128m16_kernel, 2 = gemm_pp128p_kernel (persistent), 1 = gemm_pp4w16_kernel (--experiments));  exp: PP_EXP (library built with --experiments only: 1/2/3 = gemm_pp128
     // 32x32x16 form with A3 = 1/2/0, 4 = gemm_pp4w 32x32x16, 5 = 64-byte-row 256x256, 6 = 64-byte-row 256x128 two workgroups per CU)
-    struct Variant { const char* name; int pp, glds, dbg, kern, exp; int small_ns = 3, small_blocks = 512, stagger = 0, wx = 0; };      // wx: PP_WX (MODE 7: W stream continuous across the tile boundary)
+    struct Variant { const char* name; int pp, glds, dbg, kern, exp; int small_ns = -1, small_blocks = -1, stagger = 0, wx = 0; };      // small_ns / small_blocks -1: the library's      // wx: PP_WX (MODE 7: W stream continuous across the tile boundary)
     auto apply = [](const Variant& v) {
-        moge_tune_set("GEMM_PP", v.pp); moge_tune_set("PP_MIN_TILES", 0); moge_tune_set("GLDS_VARIANT", v.glds); moge_tune_set("PP_DBG", v.dbg);
-        moge_tune_set("PP_KERN", v.kern); moge_tune_set("PP_EXP", v.exp);
-        moge_tune_set("GLDS_SMALL_NS", v.small_ns); moge_tune_set("GLDS_SMALL_BLOCKS", v.small_blocks); moge_tune_set("PP_STAGGER", v.stagger); moge_tune_set("PP_WX", v.wx);
+        tune("GEMM_PP", v.pp); tune("PP_MIN_TILES", 0); tune("GLDS_VARIANT", v.glds); tune("PP_DBG", v.dbg); tune("PP_KERN", v.kern);
+        v.small_ns < 0 ? tune_reset("GLDS_SMALL_NS") : tune("GLDS_SMALL_NS", v.small_ns);
+        v.small_blocks < 0 ? tune_reset("GLDS_SMALL_BLOCKS") : tune("GLDS_SMALL_BLOCKS", v.small_blocks);
+        tune("PP_STAGGER", v.stagger);
+#ifdef MOGE_EXPERIMENTS
+        tune("PP_EXP", v.exp); tune("PP_WX", v.wx);
+#endif
     };
     std::vector<Variant> variants = {{"glds2-m16", 0, 2, 0, 0, 0}, {"pp128-m16", 1, 2, 0, 0, 0}, {"pp128p", 1, 2, 0, 2, 0}};
     if (getenv("KB_EXP")) variants = {{"pp128-m16", 1, 2, 0, 0, 0}, {"pp4w-16", 1, 2, 0, 1, 0}, {"x:pp128-a3", 1, 2, 0, 0, 1}, {"x:pp128-a3c", 1, 2, 0, 0, 2}, {"x:pp128-2buf", 1, 2, 0, 0, 3},
@@ -448,13 +455,15 @@ static int bench_attn(const char* filter, int iters) {
         if (getenv("KB_ABL")) vars = {{"pp16", 1, 0, 0}, {"x:noguard", 1, 0, 2}, {"x:nosum", 1, 0, 16}, {"x:nosum+noguard", 1, 0, 18}, {"x:nosum+ng+noexp", 1, 0, 19}, {"x:halfVreads", 1, 0, 32},
                                       {"x:hV+nosum+ng", 1, 0, 50}, {"x:hV+nosum+ng+noexp", 1, 0, 51}};
         for (const Var& va : vars) {
-            moge_tune_set("ATTN_EXP", va.exp);
-            moge_tune_set("ATTN_VAR", va.var);
-            moge_tune_set("ATTN_KERN", va.kern == 5 ? 4 : va.kern);
-            moge_tune_set("ATTN_X_PRIO", va.kern == 5 ? 1 : 0);
-            moge_tune_set("ATTN_SK", va.sk ? 2 : 0); moge_tune_set("ATTN_SK_QB", va.sk ? va.sk : 2);
-            moge_tune_set("ATTN_KS", va.ks);
-            if (getenv("KB_SK_WGS")) moge_tune_set("ATTN_SK_WGS", atoi(getenv("KB_SK_WGS")));
+            tune("ATTN_KERN", va.kern == 5 ? 4 : va.kern);
+            tune("ATTN_KS", va.ks);
+#ifdef MOGE_EXPERIMENTS
+            tune("ATTN_EXP", va.exp);
+            tune("ATTN_VAR", va.var);
+            tune("ATTN_X_PRIO", va.kern == 5 ? 1 : 0);
+            tune("ATTN_SK", va.sk ? 2 : 0); va.sk ? tune("ATTN_SK_QB", va.sk) : tune_reset("ATTN_SK_QB");
+            if (getenv("KB_SK_WGS")) tune("ATTN_SK_WGS", atoi(getenv("KB_SK_WGS")));
+#endif
             if (va.sk) {
                 const size_t need = attention_pp_ws_bytes(c.B, c.nh, c.Ntok);
                 if (need > sk_ws_bytes) { if (sk_ws) CK(hipFree(sk_ws)); CK(hipMalloc(&sk_ws, need)); sk_ws_bytes = need; }
@@ -563,12 +572,12 @@ static int bench_conv(const char* filter, int iters) {
         gs.a = side; gs.lda = c.C; gs.w = w2; gs.ldw = c.C; gs.M = (int)px; gs.N = N; gs.K = c.C; gs.epi = EPI_STORE; gs.out = out0; gs.ldc = N;
         gs.add = out0; gs.ldadd = N;
         for (int v = 0; v < 2; v++) {
-            moge_tune_set("CONV_PP", v);
+            tune("CONV_PP", v);
             g.out = v ? out1 : out0;
             g.a2 = (v && c.side) ? side : nullptr; g.w2 = (v && c.side) ? w2 : nullptr;
             CK(hipMemsetAsync(g.out, 0, n_out * 2, st));
             int rc = launch_gemm<f16>(g, AMODE_CONV3, st);
-            if (!rc && c.side && v == 0) { moge_tune_set("GEMM_PP", 0); rc = launch_gemm<f16>(gs, AMODE_LINEAR, st); moge_tune_set("GEMM_PP", 1); }
+            if (!rc && c.side && v == 0) { tune("GEMM_PP", 0); rc = launch_gemm<f16>(gs, AMODE_LINEAR, st); tune_reset("GEMM_PP"); }
             if (rc) { printf("%s launch rc=%d\n", c.name, rc); fails++; break; }
             CK(hipStreamSynchronize(st));
             hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
@@ -583,7 +592,7 @@ static int bench_conv(const char* filter, int iters) {
             if (c.side && v == 0) {        // restore the single-pass reference result
                 CK(hipMemsetAsync(out0, 0, n_out * 2, st));
                 launch_gemm<f16>(g, AMODE_CONV3, st);
-                moge_tune_set("GEMM_PP", 0); launch_gemm<f16>(gs, AMODE_LINEAR, st); moge_tune_set("GEMM_PP", 1);
+                tune("GEMM_PP", 0); launch_gemm<f16>(gs, AMODE_LINEAR, st); tune_reset("GEMM_PP");
                 CK(hipStreamSynchronize(st));
             }
         }
@@ -600,7 +609,7 @@ static int bench_conv(const char* filter, int iters) {
         if (side) { CK(hipFree(side)); CK(hipFree(w2)); }
         CK(hipFree(in)); CK(hipFree(w)); CK(hipFree(out0)); CK(hipFree(out1)); CK(hipFree(add)); CK(hipFree(bias)); CK(hipFree(wu)); CK(hipFree(wv)); CK(hipFree(dmax)); CK(hipFree(dbad));
     }
-    moge_tune_set("CONV_PP", 1);
+    tune_reset("CONV_PP");
     return fails;
 }
 
@@ -638,7 +647,7 @@ static int bench_rb(int iters) {
         GemmArgs gr = g1; gr.act = ACT_NONE; gr.out = y1; gr.add = x; gr.rb_w2 = w2; gr.rb_bias2 = b2;
         if (!conv_rb_eligible(gr)) { printf("rb %s: not eligible\n", c.name); fails++; continue; }
         auto two = [&]() { launch_gemm<f16>(g1, AMODE_CONV3, st); launch_gemm<f16>(g2, AMODE_CONV3, st); };
-        moge_tune_set("CONV_RB_VAR", getenv("KB_RBVAR") ? atoi(getenv("KB_RBVAR")) : 0);
+        getenv("KB_RBVAR") ? tune("CONV_RB_VAR", atoi(getenv("KB_RBVAR"))) : tune_reset("CONV_RB_VAR");
         auto one = [&]() { launch_conv_rb(gr, st); };
         CK(hipMemsetAsync(y0, 0, n * 2, st)); CK(hipMemsetAsync(y1, 0xff, n * 2, st));
         two(); one();
@@ -735,7 +744,7 @@ static int bench_corun(const char* filter, int iters) {
         struct V { const char* name; int pp, glds; };
         const V vs[] = {{"pp128p (160 KiB)", 1, 2}, {"glds 128x128 (64 KiB)", 0, 2}, {"glds 128x128 1buf (32 KiB)", 0, 1}};
         for (const V& vv : vs) {
-            moge_tune_set("GEMM_PP", vv.pp); moge_tune_set("PP_MIN_TILES", 0); moge_tune_set("GLDS_VARIANT", vv.glds); moge_tune_set("PP_KERN", 2);
+            tune("GEMM_PP", vv.pp); tune("PP_MIN_TILES", 0); tune("GLDS_VARIANT", vv.glds); tune("PP_KERN", 2);
             wall(2, 2, g);                                     // warm-up
             const double tg0 = wall(1, 0, g), ta0 = wall(0, 1, g);
             const int ng = iters * (int)(ta0 / tg0 + 0.5 > 1 ? ta0 / tg0 + 0.5 : 1), nat = iters;      // roughly equal stream lengths
@@ -750,7 +759,7 @@ static int bench_corun(const char* filter, int iters) {
         }
         CK(hipFree(A)); CK(hipFree(W)); CK(hipFree(out)); CK(hipFree(bias));
     }
-    moge_tune_set("GEMM_PP", 1);
+    tune_reset("GEMM_PP");
     return 0;
 }
 

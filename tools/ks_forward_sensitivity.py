@@ -14,12 +14,9 @@ model = model_for(case).half()
 kw = dict(case["kwargs"]); kw["use_fp16"] = True
 xb = x if x.dim() == 4 else x[None]
 def run(ks, mid):
-    L.tune("ATTN_KS", ks); L.tune("ATTN_KS_MID", mid)
-    try:
+    with L.tuned(ATTN_KS=ks, ATTN_KS_MID=mid):
         f = {k: v.float().cpu().numpy() for k, v in model.forward(xb, nt).items()}
         o = {k: v.float().cpu().numpy() for k, v in model.infer(x, **kw).items()}
-    finally:
-        L.tune("ATTN_KS", 1); L.tune("ATTN_KS_MID", 0)
     return f, o
 f0, o0 = run(0, 0)
 g = {k[6:]: v for k, v in gold.items() if k.startswith("infer.")}

@@ -33,11 +33,11 @@ def main():
         for form in ("autocast", "half"):
             band = fp16_band(meta, gold, form)
             for ks, mid in [(0, 0), (1, 0)] + [(1, m) for m in (3, 6, 9, 13, 16, 19, 25, 35, 45)]:
-                L.tune("ATTN_KS", ks); L.tune("ATTN_KS_MID", mid)
                 try:
-                    out = (model.float() if form == "autocast" else model.half()).infer(x, **kw)
+                    with L.tuned(ATTN_KS=ks, ATTN_KS_MID=mid):
+                        out = (model.float() if form == "autocast" else model.half()).infer(x, **kw)
                 finally:
-                    model.float(); L.tune("ATTN_KS", 1); L.tune("ATTN_KS_MID", 0)
+                    model.float()
                 parts = []
                 for k in g:
                     a, b = subsample(k, out[k].cpu().numpy(), st), g[k]
