@@ -593,6 +593,79 @@ int moge_pano_finish(const double* x, float* distance, int H, int W, float* poin
 /* tests only: out = A in (transpose 0: in (N), out (M)) or A^T in (transpose 1: in (M), out (N)) for the masked operator above */
 int moge_test_pano_apply(int width, int height, const uint8_t* rows, int transpose, const double* in, double* out, void* stream);
 
+/* ---- training losses (reference: moge/train/losses.py; python mirror moge_amd/losses.py) --------------------------
+ * Stateless (no handle); every pointer is device memory; results are written asynchronously on `stream`.  Forward and backward of the losses
+ * that need no alignment solve.  points / gt (B, H, W, 3) fp32; a gt pixel with a non-finite component is masked out and read as 1.  loss (B)
+ * fp32 = the reference's value per image; grad_loss (B) fp32 = the incoming gradient of `loss`; the backward entries write the whole gradient
+ * (B, H, W, ...) of the prediction.  Limits: 0 <= B <= 65535, H, W >= 1, H * W < 2^31: otherwise MOGE_ERR_INVALID, as for a NULL required
+ * pointer, before anything is launched.  workspace: moge_loss_workspace(B, H, W) bytes = 8 * B * (4 * tiles + 8) with tiles =
+ * ceil(W / MOGE_LOSS_TILE_W) * ceil(H / MOGE_LOSS_TILE_H) (pure arithmetic, no GPU needed), 8-byte aligned.  Sums are fp64 over fp32 terms in a
+ * fixed order and gradients are gathered per pixel, without atomics: two calls give the same bits, and an image gives the same bits alone as
+ * inside a batch.  A mean over nothing (H = 1 or W = 1) is NaN as in torch; its gradient is zero, and edge_loss
+ * keeps the finite gradient of its other mean. */
+#define MOGE_LOSS_TILE_W 32                /* pixels of a workgroup of the stencil kernels (normal, edge): 32 x 8 */
+#define MOGE_LOSS_TILE_H 8
+#define MOGE_LOSS_SPAN 1024                /* consecutive pixels of a workgroup of the elementwise kernels */
+int moge_loss_workspace(int B, int H, int W, int64_t* bytes);
+/* losses.py:209-243 normal_loss per image: the four corner normals of every 2 x 2 quad against gt's, clamp [1, 90] degrees, smooth-L1 at 3 degrees,
+ * mean over the (H-1)(W-1) quads / (4 max(H, W)) */
+int moge_loss_normal(const float* points, const float* gt, int B, int H, int W, void* workspace, float* loss, void* stream);
+int moge_loss_normal_backward(const float* points, const float* gt, const float* grad_loss, int B, int H, int W, float* grad_points, void* stream);
+/* losses.py:246-268 edge_loss: the row and column neighbour differences against gt's, clamp [0.1, 90] degrees, (mean + mean) / (2 max(H, W)) */
+int moge_loss_edge(const float* points, const float* gt, int B, int H, int W, void* workspace, float* loss, void* stream);
+int moge_loss_edge_backward(const float* points, const float* gt, const float* grad_loss, int B, int H, int W, float* grad_points, void* stream);
+/* the per-image means of an elementwise term.  kind 0: mask_l2_loss (losses.py:271-274), 1: mask_bce_loss (:277-280, the logs clamped at -100,
+ * pred must lie in [0, 1]) - pred (B, H, W), pos / neg (B, H, W) u8, gt NULL; kind 2: normal_map_loss (:288-293) with angle_between(a, b) =
+ * atan2(|a x b|, a . b) - pred / gt (B, H, W, 3), pos / neg NULL.  grad_pred has the shape of pred. */
+int moge_loss_pixel(int kind, const float* pred, const float* gt, const uint8_t* pos, const uint8_t* neg, int B, int H, int W, void* workspace, float* loss,
+                    void* stream);
+int moge_loss_pixel_backward(int kind, const float* pred, const float* gt, const uint8_t* pos, const uint8_t* neg, const float* grad_loss, int B, int H, int W,
+                             float* grad_pred, void* stream);
+/* losses.py:283-285 metric_scale_loss over n elements: grad_out NULL: out = (log pred - log gt)^2 where gt > 0, else 0; grad_out (n): out = its
+ * gradient for pred */
+int moge_loss_metric_scale(const float* pred, const float* gt, const float* grad_out, int64_t n, float* out, void* stream);
+/* losses.py:78-109 compute_anchor_sampling_weight: points (B, H, W, 3), mask (B, H, W) u8, radius_3d (B, H, W) -> weight (B, H, W), each image
+ * summing to 1, and (count not NULL) the per-pixel counts (B, H, W) int32 before 1 / max(count, 1).  The num_test offsets of a pixel come from
+ * a counter-based hash of (seed, offset, pixel index inside the image, test index): the same (seed, offset) gives the same bits; it is not
+ * torch's randint stream.  0 <= radius_2d <= 2^24, 1 <= num_test <= 65536. */
+int moge_loss_anchor_weight(const float* points, const uint8_t* mask, const float* radius_3d, int B, int H, int W, int radius_2d, int num_test, uint64_t seed,
+                            uint64_t offset, void* workspace, int32_t* count, float* weight, void* stream);
+/* The low-resolution samples of an alignment solve: moge_metrics_lr_sample for a batch, the mask being "the gt pixel is finite" read from
+ * gt (B, H, W, 3) itself -> lr_mask (B, out_h, out_w) u8, lr_index (B, 2, out_h, out_w) int32 = (rows, cols).  1 <= out_h * out_w <= 2^24. */
+int moge_loss_lr_sample(const float* gt, int B, int H, int W, int out_h, int out_w, uint8_t* lr_mask, int32_t* lr_index, void* stream);
+/* losses.py:49-67, affine_invariant_global_loss behind its alignment solve: pred / gt (B, H, W, 3), scale (B) (0 where the solve's was not
+ * positive), shift (B, 3); weight = min(w0, 10 weighted_mean(w0, mask)) with w0 = [mask and scale > 0] / max(gt_z, 1e-5); loss (B) = the mean over
+ * H W 3 of _smooth(|scale pred + shift - gt| weight, beta), divided by (mean(mask) / lr_frac + 1e-7) when lr_frac (B) is not NULL (sparsity_aware;
+ * lr_frac = the valid fraction of the low-resolution samples); misc (B, 2) = (truncated_error, delta).  cap (B) fp32 and norm (B) fp64 are
+ * outputs the backward takes: the weight clamp and the factor between the summed terms and the loss.  The backward writes grad_pred
+ * (B, H, W, 3) for the direct path and grad_scale (B), grad_shift (B, 3) for the path through the solve.  beta >= 0. */
+int moge_loss_affine_dense(const float* pred, const float* gt, const float* scale, const float* shift, const float* lr_frac, int B, int H, int W, float beta,
+                           void* workspace, float* cap, double* norm, float* loss, float* misc, void* stream);
+int moge_loss_affine_dense_backward(const float* pred, const float* gt, const float* scale, const float* shift, const float* cap, const double* norm,
+                                    const float* grad_loss, int B, int H, int W, float beta, void* workspace, float* grad_pred, float* grad_scale, float* grad_shift,
+                                    void* stream);
+/* ---- affine_invariant_local_loss (losses.py:112-206).  P patches, SORTED by (image, anchor row): patch_image / patch_i / patch_j (P) int32 = image and
+ * anchor pixel; a patch is the S x S window, S = 2 radius_2d + 1, around its anchor, read from the full maps (nothing of shape (P, S, S, 3) is stored).
+ * 0 <= radius_2d <= 16383, B >= 1.
+ * harmonic_mean: out (B) = geometry_torch.harmonic_mean(gt_z, gt finite) per image; workspace as moge_loss_workspace.
+ * patch_mask: focal (B); mask (P, S, S) u8 = in the image, gt finite and |gt - gt_anchor| <= radius_3d = level_factor / focal * gt_anchor_z (level_factor =
+ *   0.5 / level; a non-finite anchor reads as 1); count (P) int32 = its sum, radius_3d (P).
+ * patch_lr_sample: moge_metrics_lr_sample on each patch mask -> lr_mask (P, out_h, out_w) u8, lr_index (P, 2, out_h, out_w) int32 = window (rows, cols).
+ * patch: scale (P) (0 = the patch takes no part), shift (P, 3), gt_mean (B), lr_frac (P) or NULL (sparsity_aware) -> patch_out (P, 4) fp64 workspace, norm (P)
+ *   fp64 (the backward's), loss (B) = the sum of the image's patch losses / num_patches, misc (B, 2) = (truncated_error, delta) over the image's patches.
+ * patch_backward: row_start (B * H + 1) int32 = the first patch at or after every (image, row) -> grad_pred (B, H, W, 3) whole, grad_scale (P), grad_shift
+ *   (P, 3).  A pixel sums the patches containing it in sorted order: no atomics, two calls give the same bits. */
+int moge_loss_harmonic_mean(const float* gt, int B, int H, int W, void* workspace, float* out, void* stream);
+int moge_loss_patch_mask(const float* gt, const float* focal, const int32_t* patch_image, const int32_t* patch_i, const int32_t* patch_j, int P, int B, int H, int W,
+                         int radius_2d, float level_factor, uint8_t* mask, int32_t* count, float* radius_3d, void* stream);
+int moge_loss_patch_lr_sample(const uint8_t* mask, int P, int S, int out_h, int out_w, uint8_t* lr_mask, int32_t* lr_index, void* stream);
+int moge_loss_patch(const float* pred, const float* gt, const int32_t* patch_image, const int32_t* patch_i, const int32_t* patch_j, const float* radius_3d,
+                    const uint8_t* mask, const float* scale, const float* shift, const float* gt_mean, const float* lr_frac, int P, int B, int H, int W, int radius_2d,
+                    int num_patches, float beta, double* patch_out, double* norm, float* loss, float* misc, void* stream);
+int moge_loss_patch_backward(const float* pred, const float* gt, const int32_t* patch_image, const int32_t* patch_i, const int32_t* patch_j, const uint8_t* mask,
+                             const float* scale, const float* shift, const float* gt_mean, const double* norm, const float* grad_loss, const int32_t* row_start, int P,
+                             int B, int H, int W, int radius_2d, float beta, float* grad_pred, float* grad_scale, float* grad_shift, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

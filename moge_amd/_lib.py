@@ -26,6 +26,8 @@ ABI_VERSION = 5
 MESH_MAX_MAPS, MESH_BLOCK_PX, MESH_SCAN_SPAN, MESH_NO_FACES = 8, 1024, 256, -1       # include/moge_hip.h MOGE_MESH_*
 MESH_F32, MESH_U8, MESH_UV = 0, 1, 2                                                  # moge_mesh_dtype
 PANO_MAX_VIEWS, PANO_SPAN, PANO_STATE_DOUBLES, PANO_MAX_PIXELS = 16, 1024, 64, 1 << 29  # include/moge_hip.h MOGE_PANO_*
+LOSS_TILE_W, LOSS_TILE_H, LOSS_SPAN = 32, 8, 1024                                       # include/moge_hip.h MOGE_LOSS_*
+LOSS_MASK_L2, LOSS_MASK_BCE, LOSS_NORMAL_MAP = 0, 1, 2                                  # `kind` of moge_loss_pixel
 
 
 class MogeConfig(C.Structure):
@@ -197,6 +199,25 @@ SIGNATURES = {
     "moge_pano_log": (C.c_int, [_vp, _i64, _vp, _vp]),
     "moge_pano_finish": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "moge_test_pano_apply": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "moge_loss_workspace": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "moge_loss_normal": (C.c_int, [_f32p, _f32p, _i32, _i32, _i32, _vp, _f32p, _vp]),
+    "moge_loss_normal_backward": (C.c_int, [_f32p, _f32p, _f32p, _i32, _i32, _i32, _f32p, _vp]),
+    "moge_loss_edge": (C.c_int, [_f32p, _f32p, _i32, _i32, _i32, _vp, _f32p, _vp]),
+    "moge_loss_edge_backward": (C.c_int, [_f32p, _f32p, _f32p, _i32, _i32, _i32, _f32p, _vp]),
+    "moge_loss_pixel": (C.c_int, [_i32, _f32p, _f32p, _vp, _vp, _i32, _i32, _i32, _vp, _f32p, _vp]),
+    "moge_loss_pixel_backward": (C.c_int, [_i32, _f32p, _f32p, _vp, _vp, _f32p, _i32, _i32, _i32, _f32p, _vp]),
+    "moge_loss_metric_scale": (C.c_int, [_f32p, _f32p, _f32p, _i64, _f32p, _vp]),
+    "moge_loss_anchor_weight": (C.c_int, [_f32p, _vp, _f32p, _i32, _i32, _i32, _i32, _i32, C.c_uint64, C.c_uint64, _vp, _vp, _f32p, _vp]),
+    "moge_loss_lr_sample": (C.c_int, [_f32p, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "moge_loss_affine_dense": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, C.c_float, _vp, _f32p, _vp, _f32p, _f32p, _vp]),
+    "moge_loss_harmonic_mean": (C.c_int, [_f32p, _i32, _i32, _i32, _vp, _f32p, _vp]),
+    "moge_loss_patch_mask": (C.c_int, [_f32p, _f32p, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _f32p, _vp]),
+    "moge_loss_patch_lr_sample": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "moge_loss_patch": (C.c_int, [_f32p, _f32p, _vp, _vp, _vp, _f32p, _vp, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _f32p,
+                                  _f32p, _vp]),
+    "moge_loss_patch_backward": (C.c_int, [_f32p, _f32p, _vp, _vp, _vp, _vp, _f32p, _f32p, _f32p, _vp, _f32p, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, _f32p, _f32p,
+                                           _f32p, _vp]),
+    "moge_loss_affine_dense_backward": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _vp, _f32p, _i32, _i32, _i32, C.c_float, _vp, _f32p, _f32p, _f32p, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -12,6 +12,7 @@
 // Sums are float64 in a fixed-order two-stage reduction (per-workgroup partials, then one final pass); counts are exact.  No float atomics:
 // two runs give the same bits.
 #include "common.h"
+#include "lr_sample.h"
 #include "../../include/moge_hip.h"
 
 #pragma clang fp contract(off)
@@ -48,39 +49,16 @@ __device__ __forceinline__ int find_label(const int* labels, int U, int v) {   /
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// low-resolution sampling (utils3d.pt.masked_nearest_resize(mask=..., size=(OH, OW), return_index=True); utils3d is not vendored, so this is
-// an UNPINNED convention, restated in DESIGN.md section 10 and in tools/make_metrics_golden.py):
-//   filter fh = max(1, H / OH), fw = max(1, W / OW); target centre ((j + 0.5) W / OW, (i + 0.5) H / OH); integer window ceil(fh) x ceil(fw)
-//   with top-left rint(centre - (fw / 2, fh / 2)) (half to even), clipped to the image; index = the valid pixel whose centre (x + 0.5, y + 0.5)
-//   is nearest the target centre, first in row-major window order on a tie; lr_mask = the window holds a valid pixel.  A window without a
-//   valid pixel reports its nearest in-image pixel (its value is never read through lr_mask).  Arithmetic in float64.
+// low-resolution sampling: the convention of lr_sample.h (shared with csrc/losses.hip) on one u8 mask
 // ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MET_THREADS) void lr_sample_kernel(const uint8_t* mask, int H, int W, int OH, int OW, uint8_t* lr_mask, int32_t* lr_index) {
     const int o = blockIdx.x * MET_THREADS + threadIdx.x;
     if (o >= OH * OW) return;
-    const int i = o / OW, j = o - i * OW;
-    const double fh = fmax(1.0, (double)H / OH), fw = fmax(1.0, (double)W / OW);
-    const double cy = (i + 0.5) * H / OH, cx = (j + 0.5) * W / OW;
-    const int wh = (int)ceil(fh), ww = (int)ceil(fw);
-    const int y0 = (int)rint(cy - fh / 2), x0 = (int)rint(cx - fw / 2);
-    double best_v = 1e300, best_a = 1e300;
-    int by = -1, bx = -1, ay = min(max(y0, 0), H - 1), ax = min(max(x0, 0), W - 1);
-    for (int dy = 0; dy < wh; dy++) {
-        const int y = y0 + dy;
-        if (y < 0 || y >= H) continue;
-        const double ey = y + 0.5 - cy;
-        for (int dx = 0; dx < ww; dx++) {
-            const int x = x0 + dx;
-            if (x < 0 || x >= W) continue;
-            const double ex = x + 0.5 - cx, d = ey * ey + ex * ex;
-            if (d < best_a) { best_a = d; ay = y; ax = x; }
-            if (mask[(size_t)y * W + x] && d < best_v) { best_v = d; by = y; bx = x; }
-        }
-    }
-    const bool valid = by >= 0;
+    int y, x;
+    const bool valid = lr_sample_cell(H, W, OH, OW, o, [&](int yy, int xx) { return mask[(size_t)yy * W + xx] != 0; }, y, x);
     lr_mask[o] = valid ? 1 : 0;
-    lr_index[o] = valid ? by : ay;
-    lr_index[OH * OW + o] = valid ? bx : ax;
+    lr_index[o] = y;
+    lr_index[OH * OW + o] = x;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
