@@ -497,6 +497,34 @@ int moge_eval_quantile_cut(float* depth, uint8_t* mask, int n, float q, float dr
  * (HOST pointer, 9 floats) = inv(tgt_intrinsics) */
 int moge_eval_unproject(float* depth, uint8_t* mask, int out_h, int out_w, const float* kinv, const int32_t* count, float* points, void* stream);
 
+/* ---- training data: the per-instance geometric warp (reference: moge/train/dataloader.py _process_instance and
+ * moge/utils/data_augmentation.py warp_perspective; python mirror moge_amd/train_data.py) -----------------------------
+ * Stateless (no handle); every pointer is device memory unless stated; results are written asynchronously on `stream`.  Bad sizes ->
+ * MOGE_ERR_INVALID, nothing launched.  fp32 in numpy's operation order; counts are integer atomics: two calls give the same bits.
+ * The Lanczos and sparse-nearest pre-resizes of warp_perspective are moge_eval_lanczos and moge_eval_masked_nearest above. */
+#define MOGE_TRAIN_WARP_MATS 39            /* floats of moge_train_warp's `mats` */
+/* dataloader.py:145-146 depth_map_to_normal_map(depth (H, W), normalised intrinsics, mask = isfinite, edge_threshold in degrees) -> normal
+ * (H, W, 3), camera-facing ((0, 0, -1) for a fronto-parallel plane), NaN x 3 where no face counts */
+int moge_train_normal_map(const float* depth, int H, int W, float fx, float fy, float cx, float cy, float edge_threshold_deg, float* normal, void* stream);
+/* dataloader.py:171-172 depth_map_edge(depth, mask = isfinite, kernel_size (odd, <= 15), ltol) -> eligible (H, W) fp32 = isfinite & ~edge as
+ * 0 / 1, and known (H, W) u8 = ~isnan (may be NULL) */
+int moge_train_depth_edge(const float* depth, int H, int W, int kernel_size, float ltol, float* eligible, uint8_t* known, void* stream);
+/* dataloader.py:169-192, the five cv2.warpPerspective calls fused per target pixel: image (ih, iw, 3) u8 by Lanczos-4; `nearest` (nh, nw) depth
+ * by nearest; raw_depth, eligible and normal (H, W[, 3]) by bilinear.  mats (HOST pointer, MOGE_TRAIN_WARP_MATS floats, read during the call):
+ * the inverse pixel-space matrices (target pixel -> source pixel, row-major 3x3) of the image, nearest and raw grids, then R (3x3), then
+ * inv(transform)[2, :].  A singular or non-finite matrix -> MOGE_ERR_INVALID.  -> out_u8 (out_h, out_w, 3), out_chw (3, out_h, out_w) = out_u8 / 255,
+ * out_depth (eligible == 1 ? 1 / bilinear(1 / raw) : nearest, over the z re-division), out_normal = bilinear(normal) @ R^T; flip mirrors the
+ * columns and negates normal.x; out_bilinear (u8, may be NULL) = the bilinear branch was taken; count (1 int32) = finite values of out_depth */
+int moge_train_warp(const uint8_t* image, int ih, int iw, const float* nearest, int nh, int nw, const float* raw_depth, const float* eligible, const float* normal,
+                    int H, int W, int out_h, int out_w, const float* mats, int flip, uint8_t* out_u8, float* out_chw, float* out_depth, float* out_normal,
+                    uint8_t* out_bilinear, int32_t* count, void* stream);
+/* dataloader.py:184-186, :205-219 in place on depth (n pixels), no host wait: *invalid = float64(*count) / n < 0.001, then depth = 1 everywhere;
+ * depth *= depth_unit if has_unit; max_depth = np.nanquantile(finite depths, q) * clamp_max_depth (exact, radix select); finite depths clipped to
+ * [0, max_depth]; mask_inf = isinf, mask_fin = isfinite (only_known) or ~isinf.  workspace: MOGE_EVAL_QUANTILE_WORKSPACE uint32, max_depth's
+ * float bits at workspace[5] */
+int moge_train_finish(float* depth, int n, const int32_t* count, float depth_unit, int has_unit, float q, float clamp_max_depth, int only_known,
+                      uint32_t* workspace, uint8_t* mask_fin, uint8_t* mask_inf, int32_t* invalid, void* stream);
+
 /* ---- normal-guided depth refinement (reference: moge/utils/geometry_torch.py:206-233 refine_depth_with_normal; python mirror
  * moge_amd/refine.py) ----------------------------------------------------------------------------------------------
  * Stateless (no handle); every pointer is device memory; the result is written asynchronously on `stream`.

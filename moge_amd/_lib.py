@@ -28,6 +28,7 @@ MESH_F32, MESH_U8, MESH_UV = 0, 1, 2                                            
 PANO_MAX_VIEWS, PANO_SPAN, PANO_STATE_DOUBLES, PANO_MAX_PIXELS = 16, 1024, 64, 1 << 29  # include/moge_hip.h MOGE_PANO_*
 LOSS_TILE_W, LOSS_TILE_H, LOSS_SPAN = 32, 8, 1024                                       # include/moge_hip.h MOGE_LOSS_*
 LOSS_MASK_L2, LOSS_MASK_BCE, LOSS_NORMAL_MAP = 0, 1, 2                                  # `kind` of moge_loss_pixel
+TRAIN_WARP_MATS = 39                                                                    # include/moge_hip.h MOGE_TRAIN_WARP_MATS
 
 
 class MogeConfig(C.Structure):
@@ -185,7 +186,11 @@ SIGNATURES = {
     "moge_eval_remap": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32p, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "moge_eval_quantile_cut": (C.c_int, [_vp, _vp, _i32, C.c_float, C.c_float, C.c_float, _i32, _vp, _vp, _vp]),
     "moge_eval_unproject": (C.c_int, [_vp, _vp, _i32, _i32, _f32p, _vp, _vp, _vp]),
-    "moge_refine_depth_workspace": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "moge_train_normal_map": (C.c_int, [_f32p, _i32, _i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _f32p, _vp]),
+    "moge_train_depth_edge": (C.c_int, [_f32p, _i32, _i32, _i32, C.c_float, _f32p, _vp, _vp]),
+    "moge_train_warp": (C.c_int, [_vp, _i32, _i32, _f32p, _i32, _i32, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _f32p, _i32, _vp, _f32p, _f32p, _f32p, _vp, _vp, _vp]),
+    "moge_train_finish": (C.c_int, [_f32p, _i32, _vp, C.c_float, _i32, C.c_float, C.c_float, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "moge_refine_depth_workspace":(C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
     "moge_refine_depth": (C.c_int, [_f32p, _f32p, _f32p, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _f32p, _vp]),
     "moge_image_mesh_workspace": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
     "moge_image_mesh_count": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

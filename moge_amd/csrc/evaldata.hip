@@ -13,12 +13,13 @@
 // fp32 arithmetic follows the reference's numpy operation order with NO contraction (the pragma below); Pillow's coefficients are float64
 // like its C code.  Counts use integer atomics and nothing sums floats across threads: two runs give the same bits.
 #include "common.h"
+#include "quantile.h"
 #include "../../include/moge_hip.h"
 
 #pragma clang fp contract(off)
 
-constexpr int EV_THREADS = 256;
-constexpr int EV_BLOCKS = 512;                  // grid of the grid-stride passes of the quantile
+constexpr int EV_THREADS = Q_THREADS;
+constexpr int EV_BLOCKS = Q_BLOCKS;                // grid of the grid-stride passes of the quantile (quantile.h)
 constexpr int PRECISION_BITS = 32 - 8 - 2;      // Pillow Resample.c
 constexpr int EV_SEG_BINS = MOGE_EVAL_SEG_BINS;
 
@@ -231,82 +232,22 @@ __global__ __launch_bounds__(EV_THREADS) void remap_kernel(const uint8_t* image,
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// quantile cut.  np.nanquantile(where(mask, depth, nan), q) for float32 (numpy 2.2, method 'linear', all in float32):
-//   n valid values; vi = (n - 1) q (the 'linear' method's own virtual index, not the general n q + (1 - q) - 1: the fp32 roundings differ);
-//   prev = floor(vi), next = prev + 1; vi >= n - 1 -> prev = next = n - 1 (gamma = vi + 1);
-//   gamma = vi - prev; a, b = the prev-th / next-th smallest; _lerp: d = b - a; r = a + d gamma, or b - d (1 - gamma) when gamma >= 0.5.
-// The two order statistics come from a radix select over the order-preserving bit pattern of the valid values: four 8-bit digit passes,
-// each a histogram over all pixels (integer atomics) and one single-thread scan.  No sort.  Then max_depth = r * drop_max_depth, and per
-// pixel (:168-172): mask &= depth <= max_depth, depth = nan_to_num(depth), depth *= unit; the surviving mask pixels are counted.
-// state: [0] n, [1..2] rank left, [3..4] key prefix, [5] float bits of max_depth.
+// quantile cut.  np.nanquantile(where(mask, depth, nan), q) for float32 by the radix select of quantile.h (shared with traindata.hip).
+// Then max_depth = r * drop_max_depth, and per pixel (:168-172): mask &= depth <= max_depth, depth = nan_to_num(depth), depth *= unit;
+// the surviving mask pixels are counted.  state: [0] n, [1..2] rank left, [3..4] key prefix, [5] float bits of max_depth.
 // ------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t f2key(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+struct EvValid {
+    const uint8_t* mask;
+    __device__ __forceinline__ bool operator()(int i, float d) const { return mask[i] && d == d; }
+};
 
 __global__ __launch_bounds__(EV_THREADS) void q_hist_kernel(const float* depth, const uint8_t* mask, int n, int pass, const uint32_t* state, uint32_t* hist) {
-    __shared__ uint32_t h[2][256];
-    for (int t = threadIdx.x; t < 512; t += EV_THREADS) h[t >> 8][t & 255] = 0;
-    __syncthreads();
-    const int shift = 24 - 8 * pass;
-    const uint32_t p0 = pass ? state[3] : 0, p1 = pass ? state[4] : 0;
-    for (int i = blockIdx.x * EV_THREADS + threadIdx.x; i < n; i += EV_BLOCKS * EV_THREADS) {
-        const float d = depth[i];
-        if (!mask[i] || d != d) continue;
-        const uint32_t k = f2key(d);
-        const uint32_t high = pass ? (k >> (shift + 8)) : 0u, digit = (k >> shift) & 255u;
-        if (high == p0) atomicAdd(&h[0][digit], 1u);
-        if (pass && high == p1) atomicAdd(&h[1][digit], 1u);
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < 512; t += EV_THREADS)
-        if (h[t >> 8][t & 255]) atomicAdd(&hist[t], h[t >> 8][t & 255]);
+    q_hist_body(depth, EvValid{mask}, n, pass, state, hist);
 }
 
 __global__ void q_select_kernel(int pass, float q, float drop, uint32_t* state, uint32_t* hist) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (pass == 0) {
-        uint32_t n = 0;
-        for (int b = 0; b < 256; b++) n += hist[b];
-        state[0] = n;
-        if (n == 0) { state[1] = state[2] = 0; }
-        else {
-            const float vi = (float)(n - 1) * q;
-            const bool above = vi >= (float)(n - 1);
-            const uint32_t prev = above ? n - 1 : (uint32_t)floorf(vi);
-            state[1] = prev;
-            state[2] = above ? n - 1 : prev + 1;
-        }
-        for (int b = 0; b < 256; b++) hist[256 + b] = hist[b];       // both selections start from the same histogram
-    }
-    for (int s = 0; s < 2; s++) {
-        uint32_t rank = state[1 + s], digit = 0, below = 0;
-        for (; digit < 255; digit++) {
-            const uint32_t c = hist[256 * s + digit];
-            if (below + c > rank) break;
-            below += c;
-        }
-        state[1 + s] = rank - below;
-        state[3 + s] = (state[3 + s] << 8) | digit;
-    }
-    for (int b = 0; b < 512; b++) hist[b] = 0;
-    if (pass == 3) {
-        const uint32_t n = state[0];
-        float r = __builtin_nanf("");
-        if (n) {
-            const float vi = (float)(n - 1) * q;
-            const bool above = vi >= (float)(n - 1);
-            const double prev = above ? -1.0 : (double)floorf(vi);          // numpy stores index -1 for "last" and takes gamma from it
-            const float gamma = (float)((double)vi - prev);
-            const float a = key2f(state[3]), b = key2f(state[4]);
-            const float d = b - a;
-            r = gamma >= 0.5f ? b - d * (1.f - gamma) : a + d * gamma;
-        }
-        const float md = r * drop;
-        state[5] = __float_as_uint(md);
-    }
+    q_select_body(pass, q, drop, state, hist);
 }
 
 __global__ __launch_bounds__(EV_THREADS) void q_apply_kernel(float* depth, uint8_t* mask, int n, const uint32_t* state, float unit, int has_unit, int32_t* count) {
