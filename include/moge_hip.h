@@ -694,6 +694,51 @@ int moge_loss_patch_backward(const float* pred, const float* gt, const int32_t* 
                              const float* scale, const float* shift, const float* gt_mean, const double* norm, const float* grad_loss, const int32_t* row_start, int P,
                              int B, int H, int W, int radius_2d, float beta, float* grad_pred, float* grad_scale, float* grad_shift, void* stream);
 
+/* ---- optimizer step (reference: moge/scripts/train.py:341-357, the tail behind backward(): non-finite check, clip_grad_norm_, AdamW, zero_grad,
+ * the EMA of AveragedModel, and GradScaler's unscale / update; python mirror moge_amd/optim.py) ------------------------
+ * Stateless (no handle); every pointer is device memory unless stated; work is queued on `stream`, nothing waits.  fp32 parameters, gradients
+ * and optimizer state only.
+ * table: n records of MOGE_OPTIM_SLOT_WORDS int64 words, one per tensor: 0 param, 1 grad, 2 exp_avg, 3 exp_avg_sq, 4 ema (addresses), 5 numel,
+ *   6 group index, 7 first chunk.  grad 0: the tensor has no gradient this step and is skipped entirely (as torch does); ema 0: no EMA.
+ * A workgroup owns one chunk = MOGE_OPTIM_CHUNK consecutive elements of one tensor: tensor i has ceil(numel[i] / MOGE_OPTIM_CHUNK) chunks,
+ *   numbered from first_chunk[i] = the chunks of the tensors before it (moge_optim_plan; first_chunk[n] = `chunks`, the grid).  A workgroup
+ *   finds its tensor by binary search in word 7 and bounds itself by word 5, so a chunk past its tensor's end does nothing.  16-byte loads and
+ *   stores where every address of the tensor is 16-byte aligned, single elements otherwise and for the last numel % 4; both forms do the same
+ *   arithmetic on the same element in the same order and give the same bits.
+ * state: MOGE_OPTIM_STATE_WORDS doubles: 0 applied steps, 1 skipped steps, 2 total_norm, 3 clip_coef, 4 found_nonfinite (0 / 1), 5 loss scale,
+ *   6 growth tracker, 7 the inverse loss scale the gradients of the last step were read with.
+ * hyper (HOST pointer, read during the call): groups x MOGE_OPTIM_HYPER_WORDS doubles = lr, beta1, beta2, eps, weight_decay per group,
+ *   1 <= groups <= MOGE_OPTIM_MAX_GROUPS.
+ * Bad arguments -> MOGE_ERR_INVALID with a message naming the function, before anything is launched: a NULL required pointer, n < 0, groups
+ * outside 1 .. MOGE_OPTIM_MAX_GROUPS, a beta outside [0, 1), negative (or NaN) lr / eps / weight_decay, growth_interval < 1, and a `chunks`
+ * that no plan gives (negative, above 2^31 - 1, or positive with n = 0; the table itself is device memory and is not read by the host).
+ * n = 0 or chunks = 0 is no work and no error.  Sums are fp64 in a fixed order, without atomics: two calls give the same bits. */
+#define MOGE_OPTIM_SLOT_WORDS 8            /* int64 words of a table record */
+#define MOGE_OPTIM_STATE_WORDS 8           /* doubles of the state block */
+#define MOGE_OPTIM_CHUNK 4096              /* elements of a workgroup (a power of two) */
+#define MOGE_OPTIM_MAX_GROUPS 16           /* parameter groups of a call */
+#define MOGE_OPTIM_HYPER_WORDS 5           /* doubles per group of `hyper` */
+/* host arithmetic only: numel (n, HOST) -> first_chunk (n + 1, HOST) as above.  A negative numel, or more than 2^31 - 1 chunks -> MOGE_ERR_INVALID */
+int moge_optim_plan(const int64_t* numel, int n, int64_t* first_chunk);
+/* pure arithmetic: bytes = 8 * (chunks + (chunks + 1) / 2): one fp64 sum of squares per chunk, then one uint32 flag per chunk, 8-byte aligned */
+int moge_optim_workspace(int64_t chunks, int64_t* bytes);
+/* state = all zero, loss scale = init_scale (> 0; 1 without loss scaling), inverse scale = 1 */
+int moge_optim_state_init(double* state, double init_scale, void* stream);
+/* pass 1.  Per chunk the fp64 sum of squares of fp32(g * inv_scale) (inv_scale = fp32(1 / state[5]) when use_scale, else 1) and whether a g is not
+ * finite, into workspace in chunk order; then one workgroup sums the slab in a fixed order and writes total_norm, clip_coef = min(1, max_norm /
+ * (total_norm + 1e-6)) (max_norm < 0: clipping off, 1), found_nonfinite and the inverse scale; adds 1 to the applied steps, or to the skipped steps
+ * when a gradient was not finite; and with use_scale does GradScaler.update in fp32: found -> scale *= backoff, tracker = 0; else tracker += 1 and
+ * at growth_interval scale *= growth (kept only if finite), tracker = 0.  growth, backoff > 0. */
+int moge_optim_grad_stats(const int64_t* table, int n, int64_t chunks, double max_norm, int use_scale, double growth, double backoff, int growth_interval,
+                          void* workspace, double* state, void* stream);
+/* pass 2, after pass 1 on the same stream.  With g' = fp32(fp32(g * inv_scale) * clip_coef) per element, torch.optim.AdamW in its operation order:
+ * p *= 1 - lr wd; m = lerp(m, g', 1 - beta1); v = beta2 v + (1 - beta2) g' g'; p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), IEEE sqrt and
+ * division, bc = 1 - beta^step in fp64 from the device step count, once per workgroup.  ema_decay >= 0 (< 1; < 0: none): ema = p on the first
+ * applied step, else d ema + (1 - d) p.  zero_grad: g = 0 in the same pass.  A skipped step (found_nonfinite) leaves p, m, v as they are,
+ * still zeroes g, and with ema_on_skip still blends ema towards the unchanged p. */
+int moge_optim_adamw(const int64_t* table, int n, int64_t chunks, const double* hyper, int groups, double ema_decay, int zero_grad, int ema_on_skip,
+                     const double* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ PANO_MAX_VIEWS, PANO_SPAN, PANO_STATE_DOUBLES, PANO_MAX_PIXELS = 16, 1024, 64, 1
 LOSS_TILE_W, LOSS_TILE_H, LOSS_SPAN = 32, 8, 1024                                       # include/moge_hip.h MOGE_LOSS_*
 LOSS_MASK_L2, LOSS_MASK_BCE, LOSS_NORMAL_MAP = 0, 1, 2                                  # `kind` of moge_loss_pixel
 TRAIN_WARP_MATS = 39                                                                    # include/moge_hip.h MOGE_TRAIN_WARP_MATS
+OPTIM_SLOT_WORDS, OPTIM_STATE_WORDS, OPTIM_CHUNK, OPTIM_MAX_GROUPS, OPTIM_HYPER_WORDS = 8, 8, 4096, 16, 5   # include/moge_hip.h MOGE_OPTIM_*
 
 
 class MogeConfig(C.Structure):
@@ -223,6 +224,11 @@ SIGNATURES = {
     "moge_loss_patch_backward": (C.c_int, [_f32p, _f32p, _vp, _vp, _vp, _vp, _f32p, _f32p, _f32p, _vp, _f32p, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, _f32p, _f32p,
                                            _f32p, _vp]),
     "moge_loss_affine_dense_backward": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _vp, _f32p, _i32, _i32, _i32, C.c_float, _vp, _f32p, _f32p, _f32p, _vp]),
+    "moge_optim_plan": (C.c_int, [_vp, _i32, _vp]),
+    "moge_optim_workspace": (C.c_int, [_i64, C.POINTER(_i64)]),
+    "moge_optim_state_init": (C.c_int, [_vp, C.c_double, _vp]),
+    "moge_optim_grad_stats": (C.c_int, [_vp, _i32, _i64, C.c_double, _i32, C.c_double, C.c_double, _i32, _vp, _vp, _vp]),
+    "moge_optim_adamw": (C.c_int, [_vp, _i32, _i64, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 
