@@ -739,6 +739,33 @@ int moge_optim_grad_stats(const int64_t* table, int n, int64_t chunks, double ma
 int moge_optim_adamw(const int64_t* table, int n, int64_t chunks, const double* hyper, int groups, double ema_decay, int zero_grad, int ema_on_skip,
                      const double* state, void* stream);
 
+/* ---- trainable attention of the DINOv2 blocks (reference: dinov2/layers/attention.py:70-81 and the swap of moge/model/utils.py:22-38; python
+ * mirror moge_amd/attention.py) ------------------------------------------------------------------------------------
+ * out = softmax(q k^T / 8) v per (batch, head), head_dim 64, no mask, no dropout, and its gradients.  Stateless; work is queued on `stream`,
+ * nothing waits.  dtype: MOGE_FP32 (fp32 storage, exact-fp32 MFMA) or MOGE_FP16 (fp16 storage, fp32 accumulation; the probabilities P and
+ * dS are rounded to fp16 before their second product).
+ * q, k, v (and out / dout / dq / dk / dv of the backward) are (B, nh, N, 64) tensors addressed through *_strides = {batch, head, token} element
+ * strides (HOST pointers to three int64, read during the call), the 64 of a head contiguous: the slices of a packed (B, N, 3, nh, 64)
+ * projection are read, and their gradients written, in place.  Each pointer must be 16-byte aligned and each stride a non-negative multiple
+ * of 16 bytes (8 fp16 / 4 fp32 elements).  Rows past N are never addressed.
+ * workspace: 8 B nh N bytes that the caller keeps from the forward to the backward: lse (B nh, N) fp32 = log sum_j exp(q_i k_j / 8), written
+ * by the forward, then D (B nh, N) fp32 = sum_d dout out, written by the backward.  Nothing of size N x N reaches memory.
+ * No atomics: each gradient element is summed in fp32 by one lane in tile order and rounded once, so two calls give the same bits and an
+ * image gives the bits it gives alone.
+ * Limits: B, nh >= 0, 1 <= N < 2^24, B nh ceil(N / 128) <= 2^31 - 1.  Bad arguments -> MOGE_ERR_INVALID with a message naming the function
+ * and the argument, before anything is launched.  B = 0 or nh = 0 is no work and no error, whatever the pointers. */
+/* pure arithmetic: bytes = 8 B nh N */
+int moge_attn_workspace(int B, int nh, int N, int64_t* bytes);
+/* out: (B, N, nh, 64) contiguous (token-major: its (B, N, nh 64) view is what the output projection reads); lse -> workspace */
+int moge_attn_forward(int dtype, const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v, const int64_t* v_strides,
+                      void* out, void* workspace, int B, int nh, int N, void* stream);
+/* out: what the forward wrote for the same q, k, v ({N nh 64, 64, nh 64} for its own layout); dout: the gradient of out; workspace: as the
+ * forward left it.  -> dq, dk, dv.  Three launches: D, then dk / dv (one workgroup per 128 keys, all queries), then dq (one workgroup per
+ * 128 queries, all keys). */
+int moge_attn_backward(int dtype, const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v, const int64_t* v_strides,
+                       const void* out, const int64_t* out_strides, const void* dout, const int64_t* dout_strides, void* workspace, void* dq,
+                       const int64_t* dq_strides, void* dk, const int64_t* dk_strides, void* dv, const int64_t* dv_strides, int B, int nh, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,9 @@ SIGNATURES = {
     "moge_optim_state_init": (C.c_int, [_vp, C.c_double, _vp]),
     "moge_optim_grad_stats": (C.c_int, [_vp, _i32, _i64, C.c_double, _i32, C.c_double, C.c_double, _i32, _vp, _vp, _vp]),
     "moge_optim_adamw": (C.c_int, [_vp, _i32, _i64, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp]),
+    "moge_attn_workspace": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "moge_attn_forward": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "moge_attn_backward": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 
