@@ -311,6 +311,8 @@ int moge_test_conv3x3(int precision, const float* x, const float* w, const float
  *   up2: bilinear x2 + 3x3 as the 4-phase conv + pixel shuffle, y (B,2H,2W,Cout), uv at the OUTPUT resolution    modules.py:155-159
  *   w2 != NULL: the fused residual block  y = x + conv2(relu(conv1(relu(x)) + bias)) + bias2  in ONE launch       modules.py:47-68
  *   dot_w != NULL (with up2): y[..., e] = sum_c dot_w[e][c] * fp16(up2 result[..., c]) - the level-4 output conv applied inside the resampler, modules.py:231
+ *   up2 == 2 (fp16, Cin 64, Cout 32, dot_w (dot_rows <= 12, 32)): the same output conv folded into the resampler's WEIGHTS at pack time (l4c.hip, what the model
+ *            runs): y (nd,B,2H,2W,4), nd = ceil(dot_rows / 4), y[g, ..., e] = dot_w[4 g + e] . (up2 result before any rounding, bias and uv term included); padding rows are zero
  * All pointers DEVICE fp32, NHWC maps, torch weight layouts (Cout,Cin,3,3) / side_w (Cout,Cin). */
 typedef struct moge_test_conv_args {
     int32_t precision, B, H, W, Cin, Cout;

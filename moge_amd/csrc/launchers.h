@@ -37,6 +37,18 @@ int launch_pack_dot_table(const float* w, int rows, int nd, void* tab, hipStream
 // channel zoff (= (Wo . Win4) . neck4), or null; out = remap(resize(y + z) + bias)
 int launch_head_final_dot(int kind, const float* y, const float* z, int zld, int zoff, const float* bias, float* out, int B, int Hd, int Wd, int H, int W,
                           int remap, hipStream_t st);
+// Level 4 with the output conv folded into the resampler's weights (l4c.hip): bilinear / nearest x2 + 3x3 + 1x1 rows as ONE 64 -> 16 nd conv on the low-res map.
+// in (B,H,W,64) f16; wc f16 [nd][16][576], bias / wu / wv fp32 [4 nd] from launch_l4c_pack (wu null: no uv term); out (nd,B,2H,2W,4) fp32 = one map per group,
+// read by launch_head_final_dot with a pitch of 4; uv scalars as UVTerm, for the HIGH-res grid
+struct L4cArgs {
+    const void* in; const void* wc; const float* bias; const float* wu; const float* wv; float* out;
+    int B, H, W, nd;
+    float u0, u1, ustep, v0, v1, vstep;
+};
+int launch_l4c(const L4cArgs& a, hipStream_t st);
+// w3 [32][64][3][3], d [rows][32] (rows <= 4 nd, the rest zero), bias / wu / wv [32] or null -> wc f16 [nd][16][576], vec fp32 [3][12] = d . (bias, wu, wv)
+int launch_l4c_pack(const float* w3, const float* d, int rows, int nd, int nearest, const float* bias, const float* wu, const float* wv, void* wc, float* vec,
+                    hipStream_t st);
 
 template <typename T>
 int launch_head_final_k3(int kind, const void* x4, const float* w, const float* bias, float* out, int B, int Hd, int Wd, int C, int H, int W, int remap, hipStream_t st);

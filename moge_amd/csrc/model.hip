@@ -324,11 +324,13 @@ static void build_tables_v2_decoder(moge_handle* h) {
             tadd(h, name + ".output_blocks.4.bias", cout);
             aadd(h, name + ".out4.w2", (int64_t)cout * c.dims[4]);      // output conv o level-4 input block (fp16 path, see head_final_kernel)
             aadd(h, name + ".out4.b2", cout);
-            aadd(h, name + ".dot.own", 256);                            // conv_pp fused output conv: one group of A-operand rows (512 halves), Wout
+            aadd(h, name + ".l4c.w", 16 * 576 / 2);                     // l4c.hip: Wout . (4-phase resampler weights), f16 [16][576]
+            aadd(h, name + ".l4c.v", 3 * 12);                           // ... Wout . bias (no uv term in a head)
         }
         if (neck) {
             aadd(h, "neck.dot.w2cat", 3 * 4 * 32);                      // the heads' (Wout . Win4) rows, four per head (zero padded), head order
-            aadd(h, "neck.dot", 3 * 256);                               // ... as up to three A-operand groups
+            aadd(h, "neck.l4c.w", 3 * 16 * 576 / 2);                    // l4c.hip: those rows . (the neck's 4-phase resampler weights), f16 [nheads][16][576]
+            aadd(h, "neck.l4c.v", 3 * 12);                              // ... and . (bias, wu, wv) of level 4
         }
     };
     stack("neck", true, c.neck_res_blocks, 0);
@@ -460,18 +462,23 @@ static int build_aux(moge_handle* h, hipStream_t st) {
             HIPCHK(hipMemcpyAsync(A(h, name + ".out4.w2"), w2.data(), w2.size() * 4, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(A(h, name + ".out4.b2"), b2.data(), b2.size() * 4, hipMemcpyHostToDevice, st));
             HIPCHK(hipStreamSynchronize(st));
-            // fused output conv of level 4 (conv_pp.hip DOT, fp16 path): this head's Wout as its own group, its W2 as group `ndot` of the neck's table
+            // level 4 of the fp16 path (l4c.hip): this head's W2 as group `ndot` of the neck's rows, its Wout on its own resampler
             if (c4 == 32 && co <= 4) {
-                LCHK(launch_pack_dot_table(M(h, name + ".output_blocks.4.weight"), co, 1, A(h, name + ".dot.own"), st));
                 std::vector<float> rows4(4 * 32, 0.f);
                 for (int o = 0; o < co; o++)
                     for (int j = 0; j < 32; j++) rows4[o * 32 + j] = w2[(size_t)o * c4 + j];
                 HIPCHK(hipMemcpyAsync(A(h, "neck.dot.w2cat") + ndot * 128, rows4.data(), 128 * 4, hipMemcpyHostToDevice, st));
                 HIPCHK(hipStreamSynchronize(st));
                 ndot++;
+                // ... and folded into the resampler's weights (l4c.hip, what `l4dot` of forward_impl runs): Wout . W4phase, Wout . bias
+                if (c.dims[3] == 64 && rs_is_phase(c.head_resamplers[3]))
+                    LCHK(launch_l4c_pack(M(h, name + ".resamplers.3.1.weight"), M(h, name + ".output_blocks.4.weight"), co, 1, c.head_resamplers[3] == MOGE_RS_NEAREST ? 1 : 0,
+                                         M(h, name + ".resamplers.3.1.bias"), nullptr, nullptr, A(h, name + ".l4c.w"), A(h, name + ".l4c.v"), st));
             }
         }
-    if (ndot > 0) LCHK(launch_pack_dot_table(A(h, "neck.dot.w2cat"), 4 * ndot, ndot, A(h, "neck.dot"), st));
+    if (ndot > 0 && c.dims[3] == 64 && rs_is_phase(c.neck_resamplers[3]))      // the neck's resampler under every head's Wout . Win4 (bias: resampler + level-4 input block)
+        LCHK(launch_l4c_pack(M(h, "neck.resamplers.3.1.weight"), A(h, "neck.dot.w2cat"), 4 * ndot, ndot, c.neck_resamplers[3] == MOGE_RS_NEAREST ? 1 : 0, A(h, "neck.rs3.bias2"),
+                             A(h, "neck.in4.wu"), A(h, "neck.in4.wv"), A(h, "neck.l4c.w"), A(h, "neck.l4c.v"), st));
     // ---- composed linear chains (fp16 path, `compose` in forward_impl): the bias vectors, in double on the host (one-off, a few MB of D2H) ----
     {   // neck level 0: in0(sum_k proj_k(tap_k)) = (Win0 Wout) tapcat + (Win0 sum_k b_k + b_in0) + uv term
         std::vector<float> win((size_t)c0 * (c0 + 2)), bo(c0), bi(c0), bc(c0);
@@ -828,8 +835,7 @@ static int run_gemm(moge_handle* h, const GemmArgs& g, int amode, int cls, hipSt
     case EPI_RESID: bytes += (double)g.M * g.N * (g.xres ? 8.0 + (g.x16 ? 2.0 : 0.0) : 4.0) + (g.ln_part ? (double)g.M * (g.N / 32) * 8.0 : 0.0); break;   // fp32 x read + write, fp16 copy (fp16 stream: read + write), LN partials
     case EPI_PATCH: bytes += (double)g.M * g.N * 8.0; break;                                  // + pos read, fp32 x write
     default:
-        if (g.dot_tab) bytes += (double)g.M * 4 * (16.0 * g.dot_nd);                           // fused output conv: 4 phases x 4 nd floats per low-res pixel
-        else bytes += (double)g.M * g.N * e * (g.add ? 2 : 1);                                 // STORE / QKV / CONVT: the outputs (+ the added map)
+        bytes += (double)g.M * g.N * e * (g.add ? 2 : 1);                                 // STORE / QKV / CONVT: the outputs (+ the added map)
         break;
     }
     if (cls == MOGE_KC_GEMM && amode == AMODE_LINEAR && std::is_same<T, f16>::value && gemm_runs_pp(g)) cls = MOGE_KC_GEMM_PP;
@@ -865,15 +871,27 @@ static int conv3x3(moge_handle* h, const T* in, const T* w, const float* bias, T
 // bilinear x2 + 3x3 conv as a 4-phase 3x3 conv on the low-res map (Hl,Wl), output (B,2Hl,2Wl,Cout); uv given for the HIGH-res grid
 template <typename T>
 static int conv_up2_phase(moge_handle* h, const T* in, const T* w4, const float* bias4, T* out, int B, int Hl, int Wl, int Cin, int Cout,
-                          const UVTerm* uv, hipStream_t st, const float* dot_tab = nullptr, int dot_nd = 0, float* dot_out = nullptr) {
+                          const UVTerm* uv, hipStream_t st) {
     GemmArgs g = gemm_args();
     g.a = in; g.H = Hl; g.W = Wl; g.C = Cin;
     g.w = w4; g.ldw = 9 * Cin;
     g.M = B * Hl * Wl; g.N = 4 * Cout; g.K = 9 * Cin;
     g.epi = EPI_CONVT; g.bias = bias4; g.out = out; g.Cout = Cout; g.pixW = Wl; g.pixH = Hl;
     if (uv) g.uv = *uv;
-    if (dot_tab) { g.dot_tab = dot_tab; g.dot_nd = dot_nd; g.dot_out = dot_out; g.out = nullptr; }      // fused output conv: only (B,2H,2W,4 nd) fp32 leaves the kernel
     return run_gemm<T>(h, g, AMODE_CONV3, MOGE_KC_CONV, st);
+}
+
+// level 4 with the output conv folded into the resampler's weights (l4c.hip; fp16, 64 -> 32 channels): in (B,Hl,Wl,64) -> out (nd,B,2Hl,2Wl,4) fp32.
+// Profiler: the ALGORITHMIC FLOPs of the reference's 64 -> 4 x 32 resampler (what conv_up2_phase counts; executed: 16 nd of its 128 columns), the bytes the kernel moves
+static int conv_up2_l4c(moge_handle* h, const void* in, const float* wc, const float* vec, float* out, int B, int Hl, int Wl, int nd, const UVTerm* uv, hipStream_t st) {
+    L4cArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = in; a.wc = wc; a.bias = vec; a.out = out; a.B = B; a.H = Hl; a.W = Wl; a.nd = nd;
+    if (uv) { a.wu = vec + 12; a.wv = vec + 24; a.u0 = uv->u0; a.u1 = uv->u1; a.ustep = uv->ustep; a.v0 = uv->v0; a.v1 = uv->v1; a.vstep = uv->vstep; }
+    const double npx = (double)B * Hl * Wl;
+    ProfScope ps(h, st, MOGE_KC_CONV, 2.0 * npx * 128 * 576, npx * 64 * 2 + 16.0 * nd * 576 * 2 + npx * 4 * 16.0 * nd);
+    LCHK(launch_l4c(a, st));
+    return 0;
 }
 
 template <typename T>
@@ -1201,7 +1219,8 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
     // fuse_l4: level 4 without residual blocks - the input block is folded into the output conv (head_final_kernel)
     const bool fuse_l4 = fp16 && c.head_res_blocks[MOGE_LEVELS - 1] == 0;
     // l4dot: ... and with 64 -> 32 channels on phase resamplers, out_k(x4_k + in4_k(n4)) = Wout_k x4_k + (Wout_k Win4_k) n4 + b2_k is evaluated
-    // INSIDE the two 64 -> 4 x 32 resampler convs (conv_pp.hip, fused output conv); head_final only resizes and remaps 4 + 4 floats per tap
+    // BY the two resamplers, whose weights carry Wout_k / Wout_k Win4_k since pack time (l4c.hip: 64 -> 4 phases x 4 floats per head); head_final only
+    // resizes and remaps 4 + 4 floats per tap
     const bool l4dot = fuse_l4 && c.neck_res_blocks[MOGE_LEVELS - 1] == 0 && c.dims[4] == 32 && c.dims[3] == 64 && rs_is_phase(c.neck_resamplers[3]) &&
                        rs_is_phase(c.head_resamplers[3]) && moge_tune_get(TK_CONV_PP) != 0;
     CHK(encode<T>(h, image, img_dtype, pl.H, pl.W, pl, st, !compose));
@@ -1259,8 +1278,8 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
             } else if (l == MOGE_LEVELS - 1 && l4dot) {
                 // the neck's level-4 map is only ever read through the heads' composed input block + output conv (no residual blocks at level
                 // 4): the resampler applies all of them per pixel and stores 4 floats per head instead of 32 halves
-                CHK(conv_up2_phase<T>(h, N[l - 1], P<T>(h, "neck.rs3.w3p"), A(h, "neck.rs3.bias4"), N[l], B, Hh / 2, Ww / 2, ci, co, &uvl, st, A(h, "neck.dot"), nheads,
-                                      (float*)N[l]));
+                // (the rows are folded into the resampler's weights at pack time: a 64 -> 16 nheads conv, l4c.hip)
+                CHK(conv_up2_l4c(h, N[l - 1], A(h, "neck.l4c.w"), A(h, "neck.l4c.v"), (float*)N[l], B, Hh / 2, Ww / 2, nheads, &uvl, st));
             } else {
                 CHK(conv_up2_phase<T>(h, N[l - 1], P<T>(h, S("neck.rs%d.w3p", l - 1)), A(h, S("neck.rs%d.bias4", l - 1)), N[l], B, Hh / 2, Ww / 2, ci, co, &uvl, st));
             }
@@ -1356,8 +1375,7 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
                                    ACT_NONE, nullptr, nullptr, st));
                 nxt = b2;
             } else if (l == MOGE_LEVELS - 1 && l4dot) {
-                CHK(conv_up2_phase<T>(h, Sc[cur], P<T>(h, name + ".rs3.w3p"), A(h, name + ".rs3.bias4"), Sc[a], B, Hh / 2, Ww / 2, ci, co, nullptr, st, A(h, name + ".dot.own"), 1,
-                                      (float*)Sc[a]));
+                CHK(conv_up2_l4c(h, Sc[cur], A(h, name + ".l4c.w"), A(h, name + ".l4c.v"), (float*)Sc[a], B, Hh / 2, Ww / 2, 1, nullptr, st));
                 nxt = a;
             } else {
                 CHK(conv_up2_phase<T>(h, Sc[cur], P<T>(h, name + S(".rs%d.w3p", l - 1)), A(h, name + S(".rs%d.bias4", l - 1)), Sc[a], B, Hh / 2, Ww / 2, ci, co, nullptr, st));
@@ -1378,8 +1396,8 @@ static int forward_impl(moge_handle* h, const void* image, int img_dtype, const 
         {
             ProfScope ps(h, st, MOGE_KC_POST, 0, (double)B * (rows << 4) * (cols << 4) * c.dims[4] * sizeof(T));
             if (l4dot)
-                LCHK(launch_head_final_dot(k, (const float*)Sc[cur], (const float*)N[4], 4 * nheads, 4 * head_idx, A(h, name + ".out4.b2"), outs[k], B, rows << 4, cols << 4,
-                                           pl.H, pl.W, c.remap_output, st));
+                LCHK(launch_head_final_dot(k, (const float*)Sc[cur], (const float*)N[4] + (size_t)head_idx * B * (rows << 4) * (cols << 4) * 4, 4, 0, A(h, name + ".out4.b2"),
+                                           outs[k], B, rows << 4, cols << 4, pl.H, pl.W, c.remap_output, st));      // (the neck's term: one (B,Hd,Wd,4) map per head, l4c.hip)
             else if (fuse_l4)
                 LCHK(launch_head_final<T>(k, Sc[cur], M(h, name + ".output_blocks.4.weight"), A(h, name + ".out4.b2"), N[4], A(h, name + ".out4.w2"), outs[k], B,
                                           rows << 4, cols << 4, c.dims[4], pl.H, pl.W, c.remap_output, st));

@@ -186,8 +186,33 @@ static int t_conv3(const float* x, const float* w, const float* bias, float* y, 
 
 // One 3x3 conv through the optional pieces the decoder fuses into it (conv_pp.hip flavours; gemm.hip takes the shapes / precision conv_pp
 // does not): ReLU prologue, activation, residual add, fused 1x1 side input, uv term, pixel-shuffle resampler (up2), fused residual block.
+// up2 == 2: level 4 with the 1x1 rows folded into the resampler's weights (l4c.hip): y (nd,B,2H,2W,4) fp32, nd = ceil(dot_rows / 4) <= 3,
+//   y[g, ..., e] = dot_w[4 g + e] . (conv3x3(bilinear x2 (x); w) + bias [+ wu u + wv v]),   rows >= dot_rows of the last group are zero
+static int t_l4c(const moge_test_conv_args& a, hipStream_t st) {
+    if (a.precision != MOGE_FP16 || a.Cin != 64 || a.Cout != 32 || !a.dot_w || a.dot_rows < 1 || a.dot_rows > 12 || !a.bias) return MOGE_ERR_INVALID;
+    if (a.add || a.side || a.w2 || a.relu_in || a.act || (a.wu && !a.wv)) return MOGE_ERR_INVALID;
+    const int nd = (a.dot_rows + 3) / 4, Ho = 2 * a.H, Wo = 2 * a.W;
+    const size_t nx = (size_t)a.B * a.H * a.W * 64;
+    DevBuf xb, wc, vec;
+    TCHK(xb.alloc(nx * sizeof(f16))); TCHK(wc.alloc((size_t)nd * 16 * 576 * sizeof(f16))); TCHK(vec.alloc(36 * sizeof(float)));
+    TL(to_t<f16>(a.x, xb.p, (long)nx, st));
+    TL(launch_l4c_pack(a.w, a.dot_w, a.dot_rows, nd, 0, a.bias, a.wu, a.wv, wc.p, (float*)vec.p, st));
+    L4cArgs g; memset(&g, 0, sizeof(g));
+    g.in = xb.p; g.wc = wc.p; g.bias = (const float*)vec.p; g.out = a.y; g.B = a.B; g.H = a.H; g.W = a.W; g.nd = nd;
+    if (a.wu) {
+        g.wu = (const float*)vec.p + 12; g.wv = (const float*)vec.p + 24;
+        g.u0 = a.u0; g.u1 = a.u1; g.v0 = a.v0; g.v1 = a.v1;
+        g.ustep = Wo > 1 ? (a.u1 - a.u0) / (float)(Wo - 1) : 0.f;
+        g.vstep = Ho > 1 ? (a.v1 - a.v0) / (float)(Ho - 1) : 0.f;
+    }
+    TL(launch_l4c(g, st));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
 template <typename T>
 static int t_conv_ex(const moge_test_conv_args& a, hipStream_t st) {
+    if (a.up2 == 2) return t_l4c(a, st);
     const int B = a.B, H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout, up2 = a.up2;
     const int Ho = up2 ? 2 * H : H, Wo = up2 ? 2 * W : W;
     const size_t nx = (size_t)B * H * W * Cin, ny = (size_t)B * Ho * Wo * Cout;
