@@ -299,6 +299,14 @@ typedef struct moge_test_gemm_args {
     int32_t uv_in;                                                            /* CONVT */
 } moge_test_gemm_args;
 int moge_test_gemm_ex(const moge_test_gemm_args* args, void* stream);
+/* The MOGE_TG_RESID GEMM (fp16) of the latency regime with the LayerNorm statistics finalised INSIDE the launch, as the ViT block runs proj / fc2 at small
+ * batch: the last workgroup of a row block to finish reads the block's ln_part and writes ln_mr[m] = (mean, rstd) of the updated row (eps 1e-6).
+ * xres (M,N) fp32 IN / OUT with x16 (M,N) OUT = its fp16 copy returned as fp32, or xres == NULL: x16 is the fp16 residual stream, IN / OUT as in
+ * moge_test_gemm_ex.  ln_part (M,N/32,2), ln_mr (M,2) OUT.  cnt: the caller's int32 device buffer, one counter per 64 rows, zero on entry; the kernel
+ * leaves it zero.  MOGE_ERR_INVALID when N is no multiple of 128 (the widths the producer epilogue is written for) or when the dispatch would not take that
+ * kernel for the shape (K % 64, not the throughput kernel). */
+int moge_test_gemm_fused_ln(const float* A, const float* W, const float* bias, const float* gamma, float* xres, float* x16, float* ln_part, float* ln_mr,
+                            int32_t* cnt, int M, int N, int K, void* stream);
 /* LayerNorm rows of x[rows, D], eps 1e-6 */
 int moge_test_layernorm(int precision, const float* x, const float* w, const float* b, float* y, int rows, int D, void* stream);
 /* softmax(q k^T / 8) v for q,k,v (B,nh,N,64) fp32 -> o (B,N,nh*64) */

@@ -142,6 +142,7 @@ SIGNATURES = {
     "moge_tune_value": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "moge_test_gemm": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _vp]),
     "moge_test_gemm_ex": (C.c_int, [C.POINTER(TestGemmArgs), _vp]),
+    "moge_test_gemm_fused_ln": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _vp, _i32, _i32, _i32, _vp]),
     "moge_test_layernorm": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _vp]),
     "moge_test_attention": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _vp]),
     "moge_test_conv3x3": (C.c_int, [_i32, _f32p, _f32p, _f32p, _f32p, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -594,6 +594,31 @@ int moge_test_gemm_ex(const moge_test_gemm_args* args, void* stream) {
     return args->precision == MOGE_FP16 ? t_gemm_ex<f16>(*args, st) : t_gemm_ex<float>(*args, st);
 }
 
+// EPI_RESID producer GEMM with the LayerNorm statistics finalised inside the launch (gemm_glds_kernel: GemmArgs::ln_mr_out / ln_cnt), set up as
+// the ViT block does for proj / fc2 (model.hip: `ln_done = ... gemm_fuses_ln_finalize(g)`).  A shape launch_gemm would send elsewhere is an error.
+int moge_test_gemm_fused_ln(const float* A, const float* W, const float* bias, const float* gamma, float* xres, float* x16, float* ln_part, float* ln_mr,
+                            int32_t* cnt, int M, int N, int K, void* stream) {
+    // N % 128: the producer epilogue of gemm_glds_kernel (epilogue_pair16) writes whole 128-column tiles without a column check - every ViT width is such a multiple
+    if (!A || !W || !bias || !gamma || !x16 || !ln_part || !ln_mr || !cnt || M < 1 || N < 1 || K < 1 || (K % TT<f16>::CH) || (N & 127)) return MOGE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t mn = (size_t)M * N;
+    DevBuf ab, wb, xb;
+    TCHK(ab.alloc((size_t)M * K * sizeof(f16))); TCHK(wb.alloc((size_t)N * K * sizeof(f16))); TCHK(xb.alloc(mn * sizeof(f16)));
+    TL(to_t<f16>(A, ab.p, (long)M * K, st));
+    TL(to_t<f16>(W, wb.p, (long)N * K, st));
+    if (!xres) TL((launch_convert<float, f16>(x16, xb.p, (long)mn, st)));        // fp16 residual stream: x16 is IN / OUT
+    GemmArgs g; memset(&g, 0, sizeof(g));
+    g.a = ab.p; g.lda = K; g.w = wb.p; g.ldw = K; g.M = M; g.N = N; g.K = K;
+    g.epi = EPI_RESID; g.bias = bias; g.gamma = gamma; g.xres = xres; g.ldc = N;
+    g.x16 = xb.p; g.ln_part = ln_part;
+    if (!gemm_fuses_ln_finalize(g)) return MOGE_ERR_INVALID;
+    g.ln_mr_out = ln_mr; g.ln_cnt = cnt;
+    TL(launch_gemm<f16>(g, AMODE_LINEAR, st));
+    TL((launch_convert<f16, float>(xb.p, x16, (long)mn, st)));
+    TCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
 int moge_test_layernorm(int precision, const float* x, const float* w, const float* b, float* y, int rows, int D, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (precision == MOGE_FP16) {

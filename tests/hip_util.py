@@ -108,6 +108,33 @@ def gemm_ex(kind, A, W, bias, prec=1, act=0, ln_mr=None, ln_c=None, uv=None, pix
     return out
 
 
+def gemm_fused_ln(A, W, bias, gamma, stream, half_stream=True, bufs=None, raw=False):
+    """The EPI_RESID GEMM with the LN statistics finalised inside the launch (moge_test_gemm_fused_ln).  `stream` (M, N) is the residual stream before the
+    launch: the fp16 stream of a `.half()` model (half_stream) or the fp32 one.  bufs: the dict a previous call returned - its ln_part, ln_mr and counter
+    buffers are handed to the kernel again as they are.  Returns dict(stream, x16, ln_part, ln_mr, cnt); cnt has two guard entries behind the counters."""
+    A, W, bias, gamma = _f(A), _f(W), _f(bias), _f(gamma)
+    M, K = A.shape
+    N = W.shape[0]
+    o = {}
+    if bufs is None:
+        o["ln_part"] = torch.full((M, N // 32, 2), float("nan"), device="cuda", dtype=torch.float32)
+        o["ln_mr"] = torch.full((M, 2), float("nan"), device="cuda", dtype=torch.float32)
+        o["cnt"] = torch.zeros(((M + 63) // 64 + 2,), device="cuda", dtype=torch.int32)
+    else:
+        o.update({k: bufs[k] for k in ("ln_part", "ln_mr", "cnt")})
+    x = _f(stream).clone()
+    if half_stream:
+        xres, o["x16"] = None, x
+    else:
+        xres, o["x16"] = x, torch.full((M, N), float("nan"), device="cuda", dtype=torch.float32)
+    o["stream"] = x
+    rc = L.lib.moge_test_gemm_fused_ln(_p(A), _p(W), _p(bias), _p(gamma), _p(xres), _p(o["x16"]), _p(o["ln_part"]), _p(o["ln_mr"]), _p(o["cnt"]), M, N, K, st())
+    if raw:
+        return rc
+    L.check(rc)
+    return o
+
+
 def layernorm(prec, x, w, b):
     x, w, b = _f(x), _f(w), _f(b)
     y = torch.empty_like(x)
