@@ -222,7 +222,7 @@ struct GemmArgs {
     float qscale;
     // EPI_CONVT: n = (dy*2+dx)*Cout + co -> out[((b*2H+2y+dy)*2W+2x+dx)*Cout+co]
     int Cout;
-    // LayerNorm folded into the GEMMs around it (fp16 path; model.hip "LN fold"):  LN(x) W^T + b = rstd (x W'^T - mean c) + b'
+    // LayerNorm folded into the GEMMs around it (fp16 path; model_encoder.hip "LN fold"):  LN(x) W^T + b = rstd (x W'^T - mean c) + b'
     //   with W' = g (.) W (fp16),  c[n] = sum_k W'[n][k],  b' = b + W beta.
     //   producer (EPI_RESID): x16[m*ldc+n] = fp16 copy of the UPDATED residual, ln_part[(m*(N/32) + n/32)*2 + {0,1}] = (sum, sum of
     //     squares) of its 32-column group (fixed summation tree, identical in gemm.hip and gemm_pp.hip)
@@ -292,7 +292,7 @@ inline int pp_device_cus() {
 // host-side launchers (gemm.hip, gemm_pp.hip)
 template <typename T> int launch_gemm(const GemmArgs& g, int amode, hipStream_t st);
 bool gemm_pp_eligible(const GemmArgs& g);
-// model.hip: sets the calling thread's text behind moge_last_error() and returns `code`, so a failed check is one `return`
+// model_api.hip: sets the calling thread's text behind moge_last_error() and returns `code`, so a failed check is one `return`
 int moge_internal_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 // after the launches of a stateless entry point: reads hipGetLastError() once; `what` is the whole message ("<entry>: launch failed")
 inline int launched(const char* what) {

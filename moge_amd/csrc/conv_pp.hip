@@ -70,7 +70,7 @@ __global__ __launch_bounds__(512, (BN == 64 && TW == 16 && NH == 1) ? 4 : 2) voi
     // to fp16 (what the store would have kept) and contracted with up to 3 x 4 output-conv rows by ONE small MFMA per group, block and phase:
     // the accumulator layout (lane = pixel, channels 16*jj + 4*g4 + e) is already a B operand whose K index is a permutation of the 32
     // channels; the A operand (g.dot_tab) holds the weight rows in the same permutation, replicated over the four row groups so that every
-    // lane group receives the four outputs.  modules.py:231 (+ :245 pre-composed, see model.hip): the 960 x 960 x 32 maps of level 4 were
+    // lane group receives the four outputs.  modules.py:231 (+ :245 pre-composed, see model_weights.hip): the 960 x 960 x 32 maps of level 4 were
     // 2 x 1.9 GB written and 4 x 1.9 GB read per step (head_final) for 3 + 1 useful channels.
     constexpr bool DOT = (EPI & 32) != 0;
     static_assert(!DOT || (CONVT && M16 && BN == 128), "fused output conv: the 64 -> 4 x 32 pixel-shuffle resampler");

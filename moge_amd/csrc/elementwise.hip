@@ -20,7 +20,7 @@ __device__ __forceinline__ void aa_range(int o, float scale, int in_size, int& l
 }
 __device__ __forceinline__ float tri(float x) { x = fabsf(x); return x < 1.f ? 1.f - x : 0.f; }
 
-constexpr int PATCH_K = 3 * 14 * 14;       // im2col row of a 14 x 14 RGB patch (model.hip KPATCH); the row pitch ldk pads it to a multiple of 64
+constexpr int PATCH_K = 3 * 14 * 14;       // im2col row of a 14 x 14 RGB patch (model_internal.h KPATCH); the row pitch ldk pads it to a multiple of 64
 template <typename TIn, typename TOut>
 __global__ void preprocess_kernel(const TIn* __restrict__ img, TOut* __restrict__ out, int B, int H, int W, int rows, int cols,
                                   int ldk, int nchw_out, int round16, int aa, float m0, float m1, float m2, float s0, float s1, float s2,
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const TX* __restrict__ x
     }
 }
 // --------------------------------------------------------------------------------------------
-// LayerNorm folded into the neighbouring GEMMs (fp16 path, model.hip "LN fold").
+// LayerNorm folded into the neighbouring GEMMs (fp16 path, model_encoder.hip "LN fold").
 //   ln_raw_kernel      : first block only - fp16 copy of the residual row + its (mean, rstd) (two-pass, as layernorm_kernel)
 //   ln_finalize_kernel : (sum, sum of squares) partials of the RESID epilogues -> (mean, rstd); var = E[x^2] - mean^2 in fp32, clamped at 0
 //   fold_ln_kernel     : W'[n][k] = T(g[k] * W[n][k]),  c[n] = sum_k float(W'[n][k]),  b'[n] = b[n] + sum_k beta[k] * W[n][k]
@@ -469,9 +469,9 @@ __global__ void repack_kernel(const float* src, TD* dst, int n0, int n1, int n2,
 
 // --------------------------------------------------------------------------------------------
 // CT3 (conv_pp.hip, round 6): composed weights of ConvTranspose2d(k2, s2) + 3x3.  P[(k * Cout + co)][s * Cin + ci] (fp32) holds the 36 basic products
-// W3[:, :, k] . WT[:, :, s]^T (k = ky * 3 + kx, s = sy * 2 + sx; one fp32 GEMM in model.hip); every composed matrix - the 16 (phase, tap) blocks of the interior
+// W3[:, :, k] . WT[:, :, s]^T (k = ky * 3 + kx, s = sy * 2 + sx; one fp32 GEMM in model_weights.hip); every composed matrix - the 16 (phase, tap) blocks of the interior
 // conv, the 12 x 2 (border class, cell) blocks of the border correction - is a short signed sum of them, listed per output block in a term table built on
-// the host (model.hip ct3_slots).  One rounding to fp16 per composed weight.
+// the host (model_weights.hip ct3_interior_slots / ct3_border_slots).  One rounding to fp16 per composed weight.
 // --------------------------------------------------------------------------------------------
 __global__ void ct3_combine_kernel(const float* __restrict__ P, const Ct3Slot* __restrict__ slots, int Cout, int Cin, f16* __restrict__ out, int ld) {
     const Ct3Slot sl = slots[blockIdx.y];

@@ -595,7 +595,7 @@ int moge_test_gemm_ex(const moge_test_gemm_args* args, void* stream) {
 }
 
 // EPI_RESID producer GEMM with the LayerNorm statistics finalised inside the launch (gemm_glds_kernel: GemmArgs::ln_mr_out / ln_cnt), set up as
-// the ViT block does for proj / fc2 (model.hip: `ln_done = ... gemm_fuses_ln_finalize(g)`).  A shape launch_gemm would send elsewhere is an error.
+// the ViT block does for proj / fc2 (model_encoder.hip: `ln_done = ... gemm_fuses_ln_finalize(g)`).  A shape launch_gemm would send elsewhere is an error.
 int moge_test_gemm_fused_ln(const float* A, const float* W, const float* bias, const float* gamma, float* xres, float* x16, float* ln_part, float* ln_mr,
                             int32_t* cnt, int M, int N, int K, void* stream) {
     // N % 128: the producer epilogue of gemm_glds_kernel (epilogue_pair16) writes whole 128-column tiles without a column check - every ViT width is such a multiple

@@ -287,7 +287,7 @@ class MoGeModel:
 
     # ------------------------------------------------------------------ packed master blob on disk
     # File = MAGIC | u64 header length | JSON header {model_config, nbytes, layout} | zero padding to 4096 | the fp32 master blob exactly
-    # as the library lays it out in HBM (order = f(config) only, `build_tables` in csrc/model.hip), i.e. what the RCCL broadcast ships.
+    # as the library lays it out in HBM (order = f(config) only, `build_tables` in csrc/model_weights.hip), i.e. what the RCCL broadcast ships.
     # Loading it is one H2D copy + the on-device packing kernels: no torch.load / unpickling, no per-tensor name lookup.
     BLOB_MAGIC = b"MOGE-MI355X-MASTER-BLOB-v1\n"
     MODEL_VERSION = "v2"              # recorded in the blob header: a MoGe-1 blob (same container, moge_amd/model/v1.py) is not a MoGe-2 blob

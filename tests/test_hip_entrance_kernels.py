@@ -4,7 +4,7 @@ element-wise, |got - ref| <= bound(element); where the operation is exact (paddi
 GEMMs) equality.  Every element of every returned buffer is compared.
 
 The forms of infer() that had no kernel-level test, each reached here through its own launcher:
-  preprocess_kernel as model.hip launches it (launch_preprocess: im2col scatter, K padding columns, counter zeroing, f16 output, f16 input, round16,
+  preprocess_kernel as model_encoder.hip launches it (launch_preprocess: im2col scatter, K padding columns, counter zeroing, f16 output, f16 input, round16,
       the two-tap aa = 0 branch)                                               test_preprocess, test_preprocess_counters, test_preprocess_past_the_block_cap
   EPI_PATCH (launch_gemm)                                                      test_patch_epilogue
   posembed_kernel with size_mode = 1 (launch_posembed)                         test_posembed
@@ -121,7 +121,7 @@ PRE_TYPES = [(0, 0, 0), (0, 1, 0), (1, 0, 0), (1, 1, 0), (0, 0, 1), (0, 1, 1)]  
 @pytest.mark.parametrize("aa", [1, 0])
 @pytest.mark.parametrize("in16,out16,round16", PRE_TYPES)
 def test_preprocess(H, in16, out16, round16, aa):
-    """preprocess_kernel through launch_preprocess with ldk, nchw_out = 0, round16 and aa as model.hip passes them: the im2col scatter
+    """preprocess_kernel through launch_preprocess with ldk, nchw_out = 0, round16 and aa as model_encoder.hip passes them: the im2col scatter
     out[(b Np + py cols + px) ldk + c 196 + iy 14 + ix], the zeroing of the K padding columns [588, ldk), the f16 output, the f16 input, round16 and the
     two-tap aa = 0 branch.  The nchw_out = 1 form on the same inputs must agree with it bit for bit after un-patchifying."""
     kernel = f"preprocess<{'f16' if in16 else 'f32'},{'f16' if out16 else 'f32'}>{' round16' if round16 else ''} aa={aa}"

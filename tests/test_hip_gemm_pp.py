@@ -190,7 +190,7 @@ def test_qkv_flavours_forced_pp(H, kern, B, Ntok, nh, fold):
 def test_convt_flavour_forced_pp(H, kern, B, pixH, pixW, Cin, Cout):
     """EPK_CONVT <4>: ConvTranspose2d(k2, s2) as a GEMM to 4*Cout columns + pixel-shuffle store (modules.py:162)."""
     M, N, K = B * pixH * pixW, 4 * Cout, Cin
-    A, W, b = rnd(M, K, seed=19), rnd(N, K, seed=20, scale=K ** -0.5), rnd(Cout, seed=21).repeat(4)     # bias replicated per (dy, dx), as model.hip packs it
+    A, W, b = rnd(M, K, seed=19), rnd(N, K, seed=20, scale=K ** -0.5), rnd(Cout, seed=21).repeat(4)     # bias replicated per (dy, dx), as model_weights.hip packs it
     y = (acc_ref(A, W) + b).reshape(B, pixH, pixW, 2, 2, Cout).permute(0, 1, 3, 2, 4, 5).reshape(B * 2 * pixH * 2 * pixW, Cout)
     with Force("pp", kern):
         out = H.gemm_ex(H.TG_CONVT, A, W, b, pix=(pixW, pixH), Cout=Cout)["out"].reshape(-1, Cout)

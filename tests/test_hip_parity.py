@@ -284,7 +284,7 @@ def test_properties_at_baseline_size(MoGeModel, tmp_path_factory):
 
 
 def test_batch_split_streams_are_bit_identical(MoGeModel, tmp_path_factory):
-    """The production path runs a batch >= 6 as two half batches on two internal streams (model.hip forward_dispatch);
+    """The production path runs a batch >= 6 as two half batches on two internal streams (model_v2.hip forward_dispatch);
     every image is computed independently of its batch, so the split result must equal the single-stream result."""
     from moge_amd import _lib as L
     model, cfg, sd = get_model(MoGeModel, "tiny-vits-normal", 0, True, tmp_path_factory)
@@ -367,7 +367,7 @@ def test_single_image_key_split_attention_stays_within_half_a_band(MoGeModel, tm
 
 
 def test_head_streams_are_bit_identical(MoGeModel, tmp_path_factory):
-    """Small batches run the decoder heads after the first on their own streams and scratch buffers (model.hip forward_impl,
+    """Small batches run the decoder heads after the first on their own streams and scratch buffers (model_v2.hip forward_impl,
     HEAD_STREAMS); same kernels on the same inputs: the result must equal the one-stream result, alone and inside a split batch.
     HEAD_STREAMS_MAX_B defaults to 1, so the test raises it: B = 3 forks slot 0's streams with a 3-image plan, B = 9 = 4 + 5 forks the head
     streams, events and scratch triples of BOTH sub-plans (slots 0 and 1) under BATCH_SPLIT."""
