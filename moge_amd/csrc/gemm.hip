@@ -704,10 +704,22 @@ static bool gemm_glds_eligible(const GemmArgs& g) {
     return g.N > 64 && !g.relu_in && (g.K % (8 * TT<T>::CH)) == 0;
 }
 
+// EPI_RESID with GemmArgs::x16 (the LN-fold producer, and the fp16 residual stream, which takes the same branch): epilogue_tile32 / epilogue_pair16 test
+// m < M but not n < N - they update whole 32-column groups of every column tile of the kernel and index ln_part by N / 32.  So N must be a whole number of
+// column tiles of the kernel launch_gemm<T>(g, AMODE_LINEAR) is about to take: 256 (ping-pong, by gemm_pp_eligible), 128 (gemm_glds_kernel and the wide
+// generic tile), 64 / 32 (the narrow generic tiles: N = 64 and N = 32).  Every ViT width is a multiple of 128.
+template <typename T>
+static bool resid_x16_cols_ok(const GemmArgs& g) {
+    if ((g.N & 31) != 0) return false;
+    if (std::is_same<T, f16>::value && gemm_runs_pp(g)) return true;
+    const int tile = g.N > 64 ? 128 : (g.N > 32 ? 64 : 32);          // gemm_glds_kernel (N > 64 only) and launch_by_n
+    return g.N % tile == 0;
+}
+
 // LN-fold producers (EPI_RESID + ln_part) that go to gemm_glds_kernel can finalise the statistics themselves (GemmArgs::ln_mr_out): true when launch_gemm<f16>
 // would take that kernel for g - the caller then sets ln_mr_out / ln_cnt and skips launch_ln_finalize.
 bool gemm_fuses_ln_finalize(const GemmArgs& g) {
-    if (g.epi != EPI_RESID || !g.ln_part || !g.x16 || (g.N & 63) != 0) return false;
+    if (g.epi != EPI_RESID || !g.ln_part || !g.x16 || !g.gamma || !resid_x16_cols_ok<f16>(g)) return false;
     if (gemm_runs_pp(g)) return false;
     return gemm_glds_eligible<f16>(g);
 }
@@ -717,6 +729,10 @@ int launch_gemm(const GemmArgs& g, int amode, hipStream_t st) {
     if (g.M <= 0 || g.N <= 0 || g.K <= 0) return -1;
     if ((g.K % TT<T>::CH) != 0 || (g.N % 4) != 0) return -1;
     if (amode != AMODE_LINEAR && (g.C % TT<T>::CH) != 0) return -1;
+    // what the epilogues would index without a check is refused here, before any launch
+    if (g.ln_mr && (!g.bias || !g.ln_c)) return -1;                                  // LN-fold consumer: epilogue4 loads both unconditionally
+    if (g.epi == EPI_RESID && (!g.gamma || (!g.xres && !g.x16))) return -1;
+    if (g.epi == EPI_RESID && g.x16 && (amode != AMODE_LINEAR || !resid_x16_cols_ok<T>(g))) return -1;
     switch (amode) {
     case AMODE_LINEAR:
         if constexpr (std::is_same<T, f16>::value) {

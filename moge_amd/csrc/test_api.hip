@@ -39,6 +39,10 @@ static int t_gemm(const float* A, const float* W, const float* bias, float* C, i
     return 0;
 }
 
+// Every buffer the epilogue under test is to write IN FULL starts as 0xFF bytes (NaN in fp16 and in fp32): hipMalloc routinely hands back the block the
+// previous call freed, with that call's answer still in it, so an element no store reached would otherwise compare equal to the kernel that ran before.
+static hipError_t poison(const DevBuf& b, size_t bytes, hipStream_t st) { return hipMemsetAsync(b.p, 0xFF, bytes, st); }
+
 template <typename T>
 static int t_gemm_ex(const moge_test_gemm_args& a, hipStream_t st) {
     const int M = a.M, N = a.N, K = a.K;
@@ -54,7 +58,7 @@ static int t_gemm_ex(const moge_test_gemm_args& a, hipStream_t st) {
     const size_t mn = (size_t)M * N;
     switch (a.kind) {
     case MOGE_TG_STORE:
-        TCHK(ob.alloc(mn * sizeof(T)));
+        TCHK(ob.alloc(mn * sizeof(T))); TCHK(poison(ob, mn * sizeof(T), st));
         g.epi = EPI_STORE; g.out = ob.p; g.ldc = N;
         if (a.wu) {
             g.uv.wu = a.wu; g.uv.wv = a.wv; g.uv.u0 = a.u0; g.uv.u1 = a.u1; g.uv.v0 = a.v0; g.uv.v1 = a.v1;
@@ -73,7 +77,7 @@ static int t_gemm_ex(const moge_test_gemm_args& a, hipStream_t st) {
             g.x16 = x16.p; g.ln_part = a.ln_part_out;
         } else if (a.x16_out) {
             if (!std::is_same<T, f16>::value || !a.ln_part_out) return MOGE_ERR_INVALID;
-            TCHK(x16.alloc(mn * sizeof(f16)));
+            TCHK(x16.alloc(mn * sizeof(f16))); TCHK(poison(x16, mn * sizeof(f16), st));         // output only here
             g.x16 = x16.p; g.ln_part = a.ln_part_out;
         }
         break;
@@ -85,14 +89,16 @@ static int t_gemm_ex(const moge_test_gemm_args& a, hipStream_t st) {
         // v_transposed: V^T (B,nh,64,Npad) of the fp32 parity path; v_out is IN / OUT there (the key padding [Ntok, Npad) is not the epilogue's to write)
         const size_t nv = a.v_transposed ? (size_t)(M / a.Ntok) * D * Npad : n;
         TCHK(qb.alloc(n * sizeof(T))); TCHK(kb.alloc(n * sizeof(T))); TCHK(vb.alloc(nv * sizeof(T)));
+        TCHK(poison(qb, n * sizeof(T), st)); TCHK(poison(kb, n * sizeof(T), st));
         if (a.v_transposed) TL(to_t<T>(a.v_out, vb.p, (long)nv, st));
+        else TCHK(poison(vb, nv * sizeof(T), st));
         g.epi = EPI_QKV; g.q = qb.p; g.k = kb.p; g.vT = vb.p; g.v_rowmajor = a.v_transposed ? 0 : 1;
         g.nh = a.nh; g.D = D; g.Ntok = a.Ntok; g.Npad = Npad; g.qscale = a.qscale;
         break;
     }
     case MOGE_TG_CONVT:
         if (a.Cout < 4 || (a.Cout & 3) || N != 4 * a.Cout || a.pixW < 1 || a.pixH < 1 || M % (a.pixW * a.pixH)) return MOGE_ERR_INVALID;
-        TCHK(ob.alloc(mn * sizeof(T)));
+        TCHK(ob.alloc(mn * sizeof(T))); TCHK(poison(ob, mn * sizeof(T), st));
         g.epi = EPI_CONVT; g.out = ob.p; g.Cout = a.Cout;
         if (a.wu) {          // uv_in: at the INPUT pixel, wu / wv (N) by GEMM column (MoGe-1); else at the output pixel (2 pixH, 2 pixW), wu / wv (Cout)
             const int sw = a.uv_in ? a.pixW : 2 * a.pixW, sh = a.uv_in ? a.pixH : 2 * a.pixH;
@@ -598,8 +604,8 @@ int moge_test_gemm_ex(const moge_test_gemm_args* args, void* stream) {
 // the ViT block does for proj / fc2 (model_encoder.hip: `ln_done = ... gemm_fuses_ln_finalize(g)`).  A shape launch_gemm would send elsewhere is an error.
 int moge_test_gemm_fused_ln(const float* A, const float* W, const float* bias, const float* gamma, float* xres, float* x16, float* ln_part, float* ln_mr,
                             int32_t* cnt, int M, int N, int K, void* stream) {
-    // N % 128: the producer epilogue of gemm_glds_kernel (epilogue_pair16) writes whole 128-column tiles without a column check - every ViT width is such a multiple
-    if (!A || !W || !bias || !gamma || !x16 || !ln_part || !ln_mr || !cnt || M < 1 || N < 1 || K < 1 || (K % TT<f16>::CH) || (N & 127)) return MOGE_ERR_INVALID;
+    // (N a whole number of gemm_glds_kernel's 128-column tiles, which the producer epilogue writes without a column check: gemm_fuses_ln_finalize refuses the rest)
+    if (!A || !W || !bias || !gamma || !x16 || !ln_part || !ln_mr || !cnt || M < 1 || N < 1 || K < 1 || (K % TT<f16>::CH)) return MOGE_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const size_t mn = (size_t)M * N;
     DevBuf ab, wb, xb;

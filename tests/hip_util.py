@@ -83,14 +83,14 @@ def gemm_ex(kind, A, W, bias, prec=1, act=0, ln_mr=None, ln_c=None, uv=None, pix
         out["x16"] = _f(x16_stream).clone()
         a.x16_out, a.gamma = out["x16"].data_ptr(), dev(gamma)
         if want_part:
-            out["ln_part"] = torch.empty((M, N // 32, 2), device="cuda", dtype=torch.float32)
+            out["ln_part"] = torch.full((M, N // 32, 2), float("nan"), device="cuda", dtype=torch.float32)      # the kernel writes the caller's buffer: a group it skips stays NaN
             a.ln_part_out = out["ln_part"].data_ptr()
     elif kind == TG_RESID:
         out["xres"] = _f(xres).clone()
         a.xres, a.gamma = out["xres"].data_ptr(), dev(gamma)
         if want_x16:
             out["x16"] = torch.empty((M, N), device="cuda", dtype=torch.float32)
-            out["ln_part"] = torch.empty((M, N // 32, 2), device="cuda", dtype=torch.float32)
+            out["ln_part"] = torch.full((M, N // 32, 2), float("nan"), device="cuda", dtype=torch.float32)      # the kernel writes the caller's buffer: a group it skips stays NaN
             a.x16_out, a.ln_part_out = out["x16"].data_ptr(), out["ln_part"].data_ptr()
     elif kind == TG_QKV:
         B = M // Ntok
