@@ -776,6 +776,27 @@ int moge_attn_backward(int dtype, const void* q, const int64_t* q_strides, const
                        const void* out, const int64_t* out_strides, const void* dout, const int64_t* dout_strides, void* workspace, void* dq,
                        const int64_t* dq_strides, void* dk, const int64_t* dk_strides, void* dv, const int64_t* dv_strides, int B, int nh, int N, void* stream);
 
+/* ---- trainable Linear of the DINOv2 blocks (attn.qkv, attn.proj, mlp.fc1, mlp.fc2: torch.nn.functional.linear and its gradients; python mirror
+ * moge_amd/linear.py) ------------------------------------------------------------------------------------------------
+ * y (M, N) = x (M, K) w (N, K)^T + bias (N);  dx = dy w,  dw = dy^T x,  db[n] = sum_m dy[m][n].  Stateless; work is queued on `stream`, nothing
+ * waits.  dtype: MOGE_FP32 (fp32 storage, exact-fp32 MFMA) or MOGE_FP16 (fp16 storage); every tensor, the bias included, has that storage type,
+ * every sum is fp32 and a result is rounded once.
+ * Every matrix is read or written in place through its leading dimension ld* (elements): the pointer 16-byte aligned, ld a multiple of 16 bytes
+ * (8 fp16 / 4 fp32 elements) and at least the row length.  Nothing outside [0, rows) x [0, cols) is addressed.  M >= 0 is any value (M = 0 is no
+ * work and no error, whatever the pointers); N and K are positive multiples of 16 bytes.
+ * No atomics: two calls give the same bits, and row i of y and of dx depends on row i of x / dy only.  Where dw has few tiles the contraction
+ * over M is split (the count depends on M, N, K and dtype only); the fp32 partials go to `workspace` and are added in split order.
+ * Limits: the products of ceil(. / 128) of any two of M, N, K <= 2^31 - 1 (the workgroups of a grid).  Bad arguments -> MOGE_ERR_INVALID with a
+ * message naming the function and the argument, before anything is launched. */
+/* pure arithmetic: the bytes moge_linear_backward wants for dw at these sizes; 0 where nothing is split */
+int moge_linear_workspace(int M, int N, int K, int dtype, int64_t* bytes);
+/* bias may be NULL.  One launch. */
+int moge_linear_forward(int dtype, const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy, int M, int N, int K, void* stream);
+/* dx (M, K), dw (N, K), db (N): a NULL output is not computed and costs no launch (x is read for dw only, w for dx only; workspace for a split dw
+ * only).  One launch each for dx and db, one or two (the split's second pass) for dw. */
+int moge_linear_backward(int dtype, const void* x, int64_t ldx, const void* w, int64_t ldw, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, int64_t lddw,
+                         void* db, void* workspace, int M, int N, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -233,6 +233,9 @@ SIGNATURES = {
     "moge_attn_workspace": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
     "moge_attn_forward": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "moge_attn_backward": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "moge_linear_workspace": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_i64)]),
+    "moge_linear_forward": (C.c_int, [_i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "moge_linear_backward": (C.c_int, [_i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -20,6 +20,7 @@
 // No atomics: a gradient element is summed by one lane in tile order and rounded once, so results do not depend on the batch or the grid.
 // Tails: rows past N are clamped on load (nothing outside [0, N) is ever addressed) and their P is forced to 0.
 #include "common.h"
+#include "lds_image.h"      // Vec, ldg16, lds_chunk, lds_put, lds_put_transposed
 
 namespace {
 
@@ -28,10 +29,6 @@ constexpr float AG_LN2 = 0.6931471805599453f;
 constexpr float AG_SCALE2 = AG_LOG2E * 0.125f;       // scores in log2 units: S log2(e) / sqrt(64)
 
 struct Str3 { long long b, h, n; };                   // element strides of (batch, head, token)
-
-template <typename T> struct Vec;
-template <> struct Vec<f16> { typedef f16x8 type; };
-template <> struct Vec<float> { typedef f32x4 type; };
 
 // row order in which the A operand's 32 rows are loaded so that accumulator registers [2 CH s, 2 CH s + CH) ... of lane half hi hold the
 // CH consecutive rows of chunk 2 s + hi (see attention.hip): f16 swaps bits 2 / 3, f32 is the identity
@@ -50,26 +47,6 @@ template <> __device__ __forceinline__ u32x4 ag_pack<f16>(const f32x16& p, int s
 template <> __device__ __forceinline__ u32x4 ag_pack<float>(const f32x16& p, int s) {
     f32x4 h = {p[4 * s], p[4 * s + 1], p[4 * s + 2], p[4 * s + 3]};
     return __builtin_bit_cast(u32x4, h);
-}
-
-template <typename T> __device__ __forceinline__ u32x4 ldg16(const T* p) { return *reinterpret_cast<const u32x4*>(p); }
-
-// row-major LDS image [rows][CPR chunks]: chunk c of row `row`
-template <int CPR> __device__ __forceinline__ u32x4 lds_chunk(const char* img, int row, int c) {
-    return *reinterpret_cast<const u32x4*>(img + row * (CPR * 16) + (swz<CPR>(row, c) << 4));
-}
-template <int CPR> __device__ __forceinline__ void lds_put(char* img, int row, int c, const u32x4& v) {
-    *reinterpret_cast<u32x4*>(img + row * (CPR * 16) + (swz<CPR>(row, c) << 4)) = v;
-}
-// the transposed image [64 d][CPRT chunks of tile rows]: chunk c (elements d = c CH ... c CH + CH - 1) of tile row n goes to [d][n]
-template <typename T, int CPRT> __device__ __forceinline__ void lds_put_transposed(char* img, int n, int c, const u32x4& v) {
-    constexpr int CH = TT<T>::CH;
-    const typename Vec<T>::type h = __builtin_bit_cast(typename Vec<T>::type, v);
-#pragma unroll
-    for (int e = 0; e < CH; e++) {
-        const int d = c * CH + e;
-        *reinterpret_cast<T*>(img + d * (CPRT * 16) + (swz<CPRT>(d, n / CH) << 4) + (n % CH) * (int)sizeof(T)) = h[e];
-    }
 }
 
 // ---- forward: O (B, N, nh, 64) and lse (B nh, N) ----------------------------------------------------------------------------------
