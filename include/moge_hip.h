@@ -797,6 +797,46 @@ int moge_linear_forward(int dtype, const void* x, int64_t ldx, const void* w, in
 int moge_linear_backward(int dtype, const void* x, int64_t ldx, const void* w, int64_t ldw, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, int64_t lddw,
                          void* db, void* workspace, int M, int N, int K, void* stream);
 
+/* ---- the rest of a trainable DINOv2 block: LayerNorm, exact (erf) GELU, the LayerScale residual x + r gamma, and the fused middle of a block
+ * x1 = x + r gamma, n = LayerNorm(x1); forward and backward (python mirror moge_amd/block.py) -------------------------
+ * Stateless; work is queued on `stream`, nothing waits.  Every matrix is (M, C), read or written in place through its leading dimension ld*
+ * (elements): the pointer 16-byte aligned, ld a multiple of 16 bytes (8 fp16 / 4 fp32 elements) and at least C.  Vectors (gamma, weight, bias
+ * and their gradients) are C contiguous elements, 16-byte aligned.  C is a positive multiple of 16 bytes in every storage type of the call;
+ * the LayerNorm and scale-residual entries hold a row in registers and take C <= MOGE_BLOCK_MAX_C.  M >= 0 is any value (M = 0 is no work and
+ * no error, whatever the pointers).  Nothing outside [0, M) x [0, C) is addressed.
+ * Storage types: x_dtype is the residual stream's (x, x1, y, dx, dx1, dy of the scale-residual) AND every parameter's and parameter
+ * gradient's; r_dtype the branch's (r, dr); n_dtype the normalised rows' (n, dn).  Built: r and n of x's type, or fp16 beside an fp32 stream.
+ * Sums and statistics are fp32, every result is rounded once to its tensor's type.
+ * Statistics: mean, then the mean of squared deviations, over the row held in registers; mean_rstd is (M, 2) fp32 = (mean, 1 / sqrt(var + eps)).
+ * Column sums (dweight, dbias, dgamma), no atomics: the rows are cut into slabs of S = 32 ceil(M / 16384) rows (at most 512 slabs; a function
+ * of M only), a workgroup per slab writes fp32 partials to `workspace` and a second launch adds them in a fixed order and rounds once.  Two calls
+ * give the same bits, and a row of every (M, C) output depends on that row of the inputs only.
+ * NULL output: not computed.  Nothing asked for: nothing launched, returns 0.  A call that asks for no column sum needs no workspace.
+ * Bad arguments -> MOGE_ERR_INVALID with a message naming the function and the argument, before anything is launched. */
+#define MOGE_BLOCK_MAX_C 2048
+/* pure arithmetic: bytes = 4 * 3 * ceil(M / S) * C, the partials of three column sums */
+int moge_block_workspace(int M, int C, int64_t* bytes);
+/* y = 0.5 x (1 + erf(x / sqrt 2));  dx = dy (Phi(x) + x phi(x)).  One storage type, any C. */
+int moge_block_gelu_forward(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int M, int C, void* stream);
+int moge_block_gelu_backward(int dtype, const void* x, int64_t ldx, const void* dy, int64_t lddy, void* dx, int64_t lddx, int M, int C, void* stream);
+/* y = x + r gamma.  Backward: the gradient of x is dy itself; dr = dy gamma (gamma read for dr only), dgamma = sum_m dy r (r and the workspace
+ * read for dgamma only). */
+int moge_block_scale_residual_forward(int x_dtype, int r_dtype, const void* x, int64_t ldx, const void* r, int64_t ldr, const void* gamma, void* y, int64_t ldy, int M, int C,
+                                      void* stream);
+int moge_block_scale_residual_backward(int x_dtype, int r_dtype, const void* dy, int64_t lddy, const void* r, int64_t ldr, const void* gamma, void* dr, int64_t lddr,
+                                       void* dgamma, void* workspace, int M, int C, void* stream);
+/* n = LayerNorm(x) weight + bias over C; mean_rstd may be NULL.  Fused form (r, gamma, x1 all given; all NULL: plain): x1 = x + r gamma is written
+ * with the bits of moge_block_scale_residual_forward and n = LayerNorm(x1) with the bits of the plain call on x1.  One launch. */
+int moge_block_norm_forward(int x_dtype, int r_dtype, int n_dtype, const void* x, int64_t ldx, const void* r, int64_t ldr, const void* gamma, void* x1, int64_t ldx1,
+                            const void* weight, const void* bias, float eps, void* n, int64_t ldn, void* mean_rstd, int M, int C, void* stream);
+/* x: the LayerNorm's input (fused: x1) and mean_rstd as the forward left them.  dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dn weight;
+ * dweight = sum_m dn xhat, dbias = sum_m dn (both or neither).  Fused form (gamma given): dx = dx1 + the above, dr = dx gamma, dgamma = sum_m dx r
+ * (dx before its rounding); dn or dx1 may be NULL there and counts as zero without being read (no dn: x, mean_rstd, weight are not read either and
+ * dweight, dbias come back zero).  r is read for dgamma only.  One launch, and one more where a column sum is asked for. */
+int moge_block_norm_backward(int x_dtype, int r_dtype, int n_dtype, const void* x, int64_t ldx, const void* mean_rstd, const void* weight, const void* dn, int64_t lddn,
+                             const void* dx1, int64_t lddx1, const void* r, int64_t ldr, const void* gamma, void* dx, int64_t lddx, void* dr, int64_t lddr, void* dweight,
+                             void* dbias, void* dgamma, void* workspace, int M, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

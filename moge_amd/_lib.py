@@ -29,6 +29,7 @@ PANO_MAX_VIEWS, PANO_SPAN, PANO_STATE_DOUBLES, PANO_MAX_PIXELS = 16, 1024, 64, 1
 LOSS_TILE_W, LOSS_TILE_H, LOSS_SPAN = 32, 8, 1024                                       # include/moge_hip.h MOGE_LOSS_*
 LOSS_MASK_L2, LOSS_MASK_BCE, LOSS_NORMAL_MAP = 0, 1, 2                                  # `kind` of moge_loss_pixel
 TRAIN_WARP_MATS = 39                                                                    # include/moge_hip.h MOGE_TRAIN_WARP_MATS
+BLOCK_MAX_C = 2048                                                                      # include/moge_hip.h MOGE_BLOCK_MAX_C
 OPTIM_SLOT_WORDS, OPTIM_STATE_WORDS, OPTIM_CHUNK, OPTIM_MAX_GROUPS, OPTIM_HYPER_WORDS = 8, 8, 4096, 16, 5   # include/moge_hip.h MOGE_OPTIM_*
 
 
@@ -236,6 +237,14 @@ SIGNATURES = {
     "moge_linear_workspace": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_i64)]),
     "moge_linear_forward": (C.c_int, [_i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "moge_linear_backward": (C.c_int, [_i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "moge_block_workspace": (C.c_int, [_i32, _i32, C.POINTER(_i64)]),
+    "moge_block_gelu_forward": (C.c_int, [_i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
+    "moge_block_gelu_backward": (C.c_int, [_i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
+    "moge_block_scale_residual_forward": (C.c_int, [_i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]),
+    "moge_block_scale_residual_backward": (C.c_int, [_i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "moge_block_norm_forward": (C.c_int, [_i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, C.c_float, _vp, _i64, _vp, _i32, _i32, _vp]),
+    "moge_block_norm_backward": (C.c_int, [_i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32,
+                                           _vp]),
 }
 EXPORTS = list(SIGNATURES)
 
