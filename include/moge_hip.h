@@ -837,6 +837,35 @@ int moge_block_norm_backward(int x_dtype, int r_dtype, int n_dtype, const void* 
                              const void* dx1, int64_t lddx1, const void* r, int64_t ldr, const void* gamma, void* dx, int64_t lddx, void* dr, int64_t lddr, void* dweight,
                              void* dbias, void* dgamma, void* workspace, int M, int C, void* stream);
 
+/* ---- trainable 3x3 convolution of the decoder (the replicate-padded nn.Conv2d(3, stride 1, padding 1) of the neck and the heads, and its gradients;
+ * python mirror moge_amd/conv.py) ----------------------------------------------------------------------------------------
+ * With c(i, n) = min(max(i, 0), n - 1):
+ *   y [b,p,q,o]     = bias[o] + sum_{s,t in -1..1} sum_i x[b, c(p+s,H), c(q+t,W), i] w[o,i,s+1,t+1]
+ *   dx[b,P,Q,i]     = sum over the (p, s) with c(p+s,H) = P and the (q, t) with c(q+t,W) = Q of sum_o dy[b,p,q,o] w[o,i,s+1,t+1]
+ *   dw[o,i,s+1,t+1] = sum_{b,p,q} dy[b,p,q,o] x[b, c(p+s,H), c(q+t,W), i]          db[o] = sum_{b,p,q} dy[b,p,q,o]
+ * Stateless; work is queued on `stream`, nothing waits.  dtype: MOGE_FP32 or MOGE_FP16, the storage type of every tensor (bias included); every sum
+ * is fp32 (the border terms of dx in the same accumulator as the rest) and a result is rounded once.
+ * Activations are NHWC (B, H, W, C) on a dense pixel grid, read or written in place through their pixel stride ld* (elements): pointer 16-byte
+ * aligned, ld a multiple of 16 bytes (8 fp16 / 4 fp32 elements) and at least C; the strides of W, H and B are ld, W ld and H W ld.  w and dw are
+ * torch's contiguous (Cout, Cin, 3, 3), bias and db (Cout), all 16-byte aligned.  Nothing outside [0, B H W) x [0, C) is addressed.
+ * Cin, Cout: positive multiples of 16 bytes; H, W >= 1; B >= 0 (B = 0 is no work and no error, whatever the pointers).
+ * workspace: 16-byte aligned, of the size moge_conv3x3_workspace gives for the call; its contents need not survive from one call to the next.
+ *   forward_bytes  = the weight repacked to [tap][Cout][Cin] = 9 Cin Cout elements, rounded up to 16 bytes
+ *   backward_bytes = forward_bytes + 4 * S * 9 Cin Cout (the fp32 partials of dw) + 4 * D * Cout rounded up to 16 (those of db), with
+ *     S = ceil(K / ceil(K / S0)), K = ceil(B H W / T) K tiles of T = 64 (fp16) / 32 (fp32) pixels, S0 = max(1, min(512 / (9 ceil(Cin / 128) ceil(Cout / 128)), K / 8, 64)),
+ *     D = max(1, min(ceil(B H W / 4096), 256))
+ * No atomics: the partials are added in split order, so two calls give the same bits; a pixel of y and of dx depends on its own image only.
+ * Limits: B H W <= 2^30, Cin Cout <= 2^26, ceil(B H W / 128) ceil(max(Cin, Cout) / 128) <= 2^31 - 1.  Bad arguments -> MOGE_ERR_INVALID with a message
+ * naming the function and the argument, before anything is launched. */
+int moge_conv3x3_workspace(int B, int H, int W, int Cin, int Cout, int dtype, int64_t* forward_bytes, int64_t* backward_bytes);
+/* bias may be NULL.  Two launches: the repack and the conv. */
+int moge_conv3x3_forward(int dtype, const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, int B, int H, int W, int Cin, int Cout, void* workspace,
+                         void* stream);
+/* dx (B, H, W, Cin), dw (Cout, Cin, 3, 3), db (Cout): a NULL output is not computed and costs no launch (x is read for dw only, w for dx only).  Two
+ * launches for each output that is asked for. */
+int moge_conv3x3_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, void* workspace, int B,
+                          int H, int W, int Cin, int Cout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

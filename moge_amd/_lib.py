@@ -245,6 +245,9 @@ SIGNATURES = {
     "moge_block_norm_forward": (C.c_int, [_i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, C.c_float, _vp, _i64, _vp, _i32, _i32, _vp]),
     "moge_block_norm_backward": (C.c_int, [_i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32,
                                            _vp]),
+    "moge_conv3x3_workspace": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    "moge_conv3x3_forward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "moge_conv3x3_backward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 

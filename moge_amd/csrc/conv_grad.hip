@@ -1,0 +1,480 @@
+// Trainable 3x3 convolution of the decoder (ConvStack: neck and heads): the replicate-padded nn.Conv2d(kernel 3, stride 1, padding 1) and its three
+// gradients on NHWC activations.  C ABI moge_conv3x3_*, python mirror moge_amd/conv.py, DESIGN.md section 21.
+//
+// With c(i, n) = min(max(i, 0), n - 1):
+//     y [b,p,q,o]       = bias[o] + sum_{s,t} sum_i x[b, c(p+s,H), c(q+t,W), i] w[o,i,s+1,t+1]
+//     dx[b,P,Q,i]       = sum over the (p, s) with c(p+s,H) = P and the (q, t) with c(q+t,W) = Q of sum_o dy[b,p,q,o] w[o,i,s+1,t+1]
+//     dw[o,i,s+1,t+1]   = sum_{b,p,q} dy[b,p,q,o] x[b, c(p+s,H), c(q+t,W), i]
+//     db[o]             = sum_{b,p,q} dy[b,p,q,o]
+// All three are the product family of linear_grad.hip, C[i][j] = sum_k A(i, k) B(j, k), on the same 128 x 128 workgroup tile, K tiles, LDS images and
+// MFMA loop (lds_image.h), with the rows of an activation operand GATHERED: row m = (b H + P) W + Q of a dense pixel grid reads pixel m + dP W + dQ.
+//     forward  A = x at the clamped pixel          B = w[tap] as (Cout, Cin)            9 steps x Cin             conv_kernel<T, false>
+//     dgrad    A = dy at (P - s, Q - t), or zero   B = w[tap] read as (Cin, Cout)       9 (+ 16) steps x Cout     conv_kernel<T, true>
+//     wgrad    A = dy read as (Cout, pixels)       B = clamped x read as (Cin, pixels)  pixels, split             conv_wgrad_kernel<T>
+// The weight's Cin stride is 9 elements: conv_repack_kernel copies it (exactly) to [tap][Cout][Cin] in the workspace first.
+//
+// dgrad border rule.  Per axis an index P has exactly three (p, s): (P + 1, -1), (P, 0), (P - 1, +1) inside the image, and where one of them falls outside,
+// replicate padding gives the border pixel itself instead: (0, -1) at P = 0 and (H - 1, +1) at P = H - 1.  An axis therefore has five step kinds: the three
+// zero-masked gathers and two border kinds whose A rows are zero except on the border line.  The 9 + 16 combinations go into ONE fp32 accumulator; a
+// combination with a border kind runs only in workgroups whose 128 pixels touch that border (decided from the tile's pixel range, wave-uniform).
+//
+// wgrad: grid = tiles of (Cout, Cin) x 9 taps x conv_split; every workgroup writes an fp32 partial [split][tap][Cout][Cin] to the workspace and
+// conv_reduce_kernel adds them in split order into torch's (Cout, Cin, 3, 3) layout, rounding once.  db: fp32 column sums of slabs of rows, added in slab
+// order.  Both splits are functions of the sizes only.  No atomics anywhere: two calls give the same bits.
+// Tails: as linear_grad.hip - a pixel row past B H W is clamped where it is a row of C and zero where it is the contraction index, a chunk past the
+// contraction range is zero, nothing outside [0, B H W) x [0, C) is addressed, stores are guarded.  Offsets are 64-bit.
+#include "common.h"
+#include "lds_image.h"
+
+namespace {
+
+__device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
+// One axis of a contraction step, kind a.  Forward: a = s + 1, the source is c(P + s).  dgrad: a < 3 is s = a - 1 with the source P - s where that is
+// inside; a = 3 is (p, s) = (0, -1), which exists at P = 0 only; a = 4 is (n - 1, +1), at P = n - 1 only.  d: source index minus P.
+template <bool DG> __device__ __forceinline__ int axis_tap(int a) { return !DG || a < 3 ? a : (a == 3 ? 0 : 2); }
+template <bool DG> __device__ __forceinline__ bool axis_src(int a, int P, int n, int& d) {
+    if (!DG) {
+        d = clampi(P + a - 1, n) - P;
+        return true;
+    }
+    d = a < 3 ? 1 - a : 0;
+    return a < 3 ? (unsigned)(P + d) < (unsigned)n : (a == 3 ? P == 0 : P == n - 1);
+}
+
+// the 128 pixel rows x LCPR chunks of the gathered activation operand for step `opt`, channel chunk at k: 4 chunks per thread (the rows of lin_load<T, false>)
+template <typename T, bool DG>
+__device__ __forceinline__ void conv_load(u32x4 (&r)[4], const T* __restrict__ p, long long ld, const int (&m)[4], const int (&P)[4], const int (&Q)[4], int H, int W,
+                                          int opt, int k, int kend) {
+    constexpr int NA = DG ? 5 : 3;
+    const int a = opt / NA, b = opt - a * NA;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        int dp, dq;
+        const bool ok = axis_src<DG>(a, P[i], H, dp) & axis_src<DG>(b, Q[i], W, dq);
+        r[i] = u32x4{0u, 0u, 0u, 0u};
+        if (ok && k < kend) r[i] = ldg16(p + ((long long)m[i] + dp * W + dq) * ld + k);
+    }
+}
+
+// does [m0, m1] hold an index that is 0 (hi false) or n - 1 (hi true) modulo n
+__device__ __forceinline__ bool range_hits(long long m0, long long m1, int n, bool hi) {
+    const long long o = hi ? 1 : 0;
+    return (m0 + o + n - 1) / n * n <= m1 + o;
+}
+
+// the 2 x 2 mma_step tiles of a wave over one staged K tile (linear_kernel's loop)
+template <typename T>
+__device__ __forceinline__ void conv_mma(f32x16 (&acc)[2][2], const char* sA, const char* sB, int wi, int wj, int l31, int hi) {
+#pragma unroll
+    for (int s = 0; s < LCPR / 2; s++) {
+        u32x4 fa[2], fb[2];
+#pragma unroll
+        for (int a = 0; a < 2; a++) fa[a] = lds_chunk<LCPR>(sA, wi + a * 32 + l31, (2 * s + hi) ^ lin_x(wi + a * 32 + l31));
+#pragma unroll
+        for (int b = 0; b < 2; b++) fb[b] = lds_chunk<LCPR>(sB, wj + b * 32 + l31, (2 * s + hi) ^ lin_x(wj + b * 32 + l31));
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int b = 0; b < 2; b++) mma_step<T>(acc[a][b], fb[b], fa[a]);
+    }
+}
+
+__device__ __forceinline__ void conv_zero(f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
+}
+
+// the row of C on the lane, its columns in the registers: four consecutive columns per store (linear_kernel's epilogue)
+template <typename TO, typename TB>
+__device__ __forceinline__ void conv_store(const f32x16 (&acc)[2][2], TO* __restrict__ C, long long ldc, const TB* __restrict__ bias, int i0, int I, int j0, int J, int wi, int wj,
+                                           int l31, int hi) {
+#pragma unroll
+    for (int a = 0; a < 2; a++) {
+        const int i = i0 + wi + a * 32 + l31;
+        if (i >= I) continue;
+        TO* crow = C + i * ldc;
+#pragma unroll
+        for (int b = 0; b < 2; b++)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; g4++) {
+                const int j = j0 + wj + b * 32 + 8 * g4 + 4 * hi;
+                if (j >= J) continue;                                   // J is a multiple of 4: a group of four is inside or outside
+                float bv[4] = {0.f, 0.f, 0.f, 0.f};
+                if (bias) load4(bias + j, bv);
+                store4(crow + j, acc[a][b][4 * g4] + bv[0], acc[a][b][4 * g4 + 1] + bv[1], acc[a][b][4 * g4 + 2] + bv[2], acc[a][b][4 * g4 + 3] + bv[3]);
+            }
+    }
+}
+
+// forward (DG false): C = y, A = x, Kc = Cin, J = Cout.  dgrad (DG true): C = dx, A = dy, Kc = Cout, J = Cin.  wp: [tap][Cout][Cin].  M = B H W pixels.
+template <typename T, bool DG>
+__global__ __launch_bounds__(256) void conv_kernel(const T* __restrict__ A, long long lda, const T* __restrict__ wp, const T* __restrict__ bias, T* __restrict__ C,
+                                                   long long ldc, int M, int H, int W, int Kc, int J, int tiles_j) {
+    constexpr int CH = TT<T>::CH;
+    constexpr int BK = LCPR * CH;
+    constexpr int NA = DG ? 5 : 3;
+    __shared__ __attribute__((aligned(16))) char sA[LT * LCPR * 16];      // [pixel][k]
+    __shared__ __attribute__((aligned(16))) char sB[LT * LCPR * 16];      // [j][k]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int hi = lane >> 5, l31 = lane & 31;
+    const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
+    const int i0 = ti * LT, j0 = tj * LT;
+    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+
+    // the steps this workgroup runs: all of the forward's 9; of the dgrad's 25, a border kind only where the tile's pixels touch that border
+    unsigned mask = 0x1ffu;
+    if (DG) {
+        const long long m1 = (long long)i0 + LT - 1 < M ? (long long)i0 + LT - 1 : M - 1;
+        const bool q_lo = range_hits(i0, m1, W, false), q_hi = range_hits(i0, m1, W, true);
+        const bool p_lo = range_hits(i0 / W, m1 / W, H, false), p_hi = range_hits(i0 / W, m1 / W, H, true);
+        mask = 0;
+        for (int a = 0; a < 5; a++)
+            for (int b = 0; b < 5; b++)
+                if ((a < 3 || (a == 3 ? p_lo : p_hi)) && (b < 3 || (b == 3 ? q_lo : q_hi))) mask |= 1u << (a * 5 + b);
+    }
+
+    // the four pixel rows a thread loads in every step
+    int m[4], P[4], Q[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int g = i0 + (tid + i * 256) / LCPR;
+        m[i] = g < M ? g : M - 1;
+        const int row = m[i] / W;
+        Q[i] = m[i] - row * W;
+        P[i] = row % H;
+    }
+    const int kc = (tid % LCPR) * CH;
+    const long long wtap = (long long)Kc * J;
+
+    f32x16 acc[2][2];
+    conv_zero(acc);
+
+    u32x4 ra[4], rb[4];
+    int opt = 0, k0 = 0;                                                  // step 0 is in every mask
+    conv_load<T, DG>(ra, A, lda, m, P, Q, H, W, opt, kc, Kc);
+    lin_load<T, DG>(rb, wp + (axis_tap<DG>(0) * 3 + axis_tap<DG>(0)) * wtap, DG ? J : Kc, j0, J, 0, Kc, tid);
+    while (true) {
+        __syncthreads();                 // everyone finished reading the previous tile
+        lin_stage<T, false>(sA, ra, tid);
+        lin_stage<T, DG>(sB, rb, tid);
+        __syncthreads();
+        int nopt = opt, nk = k0 + BK;
+        if (nk >= Kc) {
+            const unsigned rest = mask >> (opt + 1);
+            nk = 0;
+            nopt = rest ? opt + 1 + __builtin_ctz(rest) : -1;
+        }
+        if (nopt >= 0) {
+            const int a = nopt / NA, b = nopt - a * NA;
+            conv_load<T, DG>(ra, A, lda, m, P, Q, H, W, nopt, nk + kc, Kc);
+            lin_load<T, DG>(rb, wp + (axis_tap<DG>(a) * 3 + axis_tap<DG>(b)) * wtap, DG ? J : Kc, j0, J, nk, Kc, tid);
+        }
+        conv_mma<T>(acc, sA, sB, wi, wj, l31, hi);
+        if (nopt < 0) break;
+        opt = nopt;
+        k0 = nk;
+    }
+    conv_store<T, T>(acc, C, ldc, bias, i0, M, j0, J, wi, wj, l31, hi);
+}
+
+// part[z][tap][Cout][Cin] = sum over the pixels [z kper, min(M, (z + 1) kper)) of dy[m][o] x[src(m, tap)][i]; tap = blockIdx.y, z = blockIdx.z
+template <typename T>
+__global__ __launch_bounds__(256) void conv_wgrad_kernel(const T* __restrict__ dy, long long lddy, const T* __restrict__ x, long long ldx, float* __restrict__ part, int M,
+                                                         int H, int W, int Cout, int Cin, int kper, int tiles_j) {
+    constexpr int CH = TT<T>::CH;
+    constexpr int BK = LCPR * CH;
+    constexpr int RC = LT / CH;
+    __shared__ __attribute__((aligned(16))) char sA[LT * LCPR * 16];      // [o][pixel]
+    __shared__ __attribute__((aligned(16))) char sB[LT * LCPR * 16];      // [i][pixel]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int hi = lane >> 5, l31 = lane & 31;
+    const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
+    const int i0 = ti * LT, j0 = tj * LT;
+    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+    const int tap = blockIdx.y, s = tap / 3 - 1, t = tap - (tap / 3) * 3 - 1;
+    const int kbeg = blockIdx.z * kper;
+    const int kend = M - kbeg < kper ? M : kbeg + kper;
+
+    // the four pixels of a K tile whose x chunks a thread loads: (P, Q) advance by BK pixels per tile
+    int P[4], Q[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int k = kbeg + (tid + i * 256) / RC;
+        const int row = k / W;
+        Q[i] = k - row * W;
+        P[i] = row % H;
+    }
+    const int g = j0 + ((tid % RC) * CH);                                // the thread's channel chunk of x
+
+    auto load_x = [&](u32x4 (&r)[4], int k0) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int k = k0 + (tid + i * 256) / RC;
+            r[i] = u32x4{0u, 0u, 0u, 0u};
+            if (k < kend && g < Cin) r[i] = ldg16(x + ((long long)k + (clampi(P[i] + s, H) - P[i]) * W + (clampi(Q[i] + t, W) - Q[i])) * ldx + g);
+            Q[i] += BK;
+            if (Q[i] >= W) {
+                const int c = Q[i] / W;
+                Q[i] -= c * W;
+                P[i] = (P[i] + c) % H;
+            }
+        }
+    };
+
+    f32x16 acc[2][2];
+    conv_zero(acc);
+
+    u32x4 ra[4], rb[4];
+    lin_load<T, true>(ra, dy, lddy, i0, Cout, kbeg, kend, tid);
+    load_x(rb, kbeg);
+    for (int k0 = kbeg; k0 < kend; k0 += BK) {
+        __syncthreads();
+        lin_stage<T, true>(sA, ra, tid);
+        lin_stage<T, true>(sB, rb, tid);
+        __syncthreads();
+        if (k0 + BK < kend) {
+            lin_load<T, true>(ra, dy, lddy, i0, Cout, k0 + BK, kend, tid);
+            load_x(rb, k0 + BK);
+        }
+        conv_mma<T>(acc, sA, sB, wi, wj, l31, hi);
+    }
+    conv_store<float, float>(acc, part + ((long long)blockIdx.z * 9 + tap) * Cout * Cin, Cin, nullptr, i0, Cout, j0, Cin, wi, wj, l31, hi);
+}
+
+// wp[tap][o][i] = w[o][i][tap]: an exact copy, one thread per (o, i)
+template <typename T>
+__global__ __launch_bounds__(256) void conv_repack_kernel(const T* __restrict__ w, T* __restrict__ wp, int n) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) wp[(long long)tap * n + e] = w[(long long)e * 9 + tap];
+}
+
+// dw[o][i][tap] = the S partials added in split order, rounded once; one thread per (o, i)
+template <typename T>
+__global__ __launch_bounds__(256) void conv_reduce_kernel(const float* __restrict__ part, T* __restrict__ dw, int n, int S) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) {
+        float v = part[(long long)tap * n + e];
+        for (int z = 1; z < S; z++) v += part[((long long)z * 9 + tap) * n + e];
+        dw[(long long)e * 9 + tap] = (T)v;
+    }
+}
+
+// part[z][o] = sum of dy[m][o] over the slab of rows [z rows, min(M, (z + 1) rows)): a workgroup takes 8 column chunks, 32 threads per chunk sum the
+// rows r, r + 32, ... of the slab in that order, then the 32 partials are added in the order r = 0 ... 31 (lin_colsum_kernel's order, per slab)
+template <typename T>
+__global__ __launch_bounds__(256) void conv_colsum_kernel(const T* __restrict__ dy, long long lddy, float* __restrict__ part, int M, int N, int rows) {
+    constexpr int CH = TT<T>::CH;
+    __shared__ float sum[32][8 * CH + 1];
+    const int tid = threadIdx.x, c = tid & 7, r = tid >> 3;
+    const int n = (blockIdx.x * 8 + c) * CH;
+    const int mbeg = blockIdx.y * rows;
+    const int mend = M - mbeg < rows ? M : mbeg + rows;
+    float s[CH];
+#pragma unroll
+    for (int e = 0; e < CH; e++) s[e] = 0.f;
+    if (n < N)
+        for (int m = mbeg + r; m < mend; m += 32) {
+            const typename Vec<T>::type v = __builtin_bit_cast(typename Vec<T>::type, ldg16(dy + m * lddy + n));
+#pragma unroll
+            for (int e = 0; e < CH; e++) s[e] += (float)v[e];
+        }
+#pragma unroll
+    for (int e = 0; e < CH; e++) sum[r][c * CH + e] = s[e];
+    __syncthreads();
+    if (tid < 8 * CH) {
+        const int col = blockIdx.x * 8 * CH + tid;
+        if (col < N) {
+            float v = sum[0][tid];
+            for (int i = 1; i < 32; i++) v += sum[i][tid];
+            part[(long long)blockIdx.y * N + col] = v;
+        }
+    }
+}
+
+// db[o] = the slab sums added in slab order, rounded once
+template <typename T>
+__global__ __launch_bounds__(256) void conv_colsum_reduce_kernel(const float* __restrict__ part, T* __restrict__ db, int N, int S) {
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= N) return;
+    float v = part[o];
+    for (int z = 1; z < S; z++) v += part[(long long)z * N + o];
+    db[o] = (T)v;
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------
+constexpr int CONV_MAX_SPLIT = 64;
+constexpr int CONV_FILL = 512;             // workgroups wgrad aims for: a constant, not the device's CU count, so that the bits do not depend on the device
+constexpr int CONV_MIN_KTILES = 8;         // K tiles (of 64 fp16 / 32 fp32 pixels) a split keeps at least
+constexpr int CONV_DB_ROWS = 4096;         // pixels of a db slab at the least
+constexpr int CONV_DB_MAX = 256;           // slabs at the most
+constexpr long long CONV_MAX_PIXELS = 1LL << 30;
+
+inline long long tiles(long long n) { return (n + LT - 1) / LT; }
+inline int chunk_of(int dtype) { return dtype == MOGE_FP16 ? 8 : 4; }
+inline long long align16(long long n) { return (n + 15) / 16 * 16; }
+
+// wgrad's split of the pixels: a function of (B H W, Cin, Cout, dtype) only.  `per` K tiles to a part, `parts` parts that have work (the last one takes
+// what is left); the workspace query and the launch both read this one result.
+struct ConvSplit { int parts; long long per; };
+ConvSplit conv_split(long long M, int Cin, int Cout, int dtype) {
+    const long long t = 9 * tiles(Cout) * tiles(Cin);
+    const long long ktiles = (M + LCPR * chunk_of(dtype) - 1) / (LCPR * chunk_of(dtype));
+    long long s = CONV_FILL / t;
+    if (s > ktiles / CONV_MIN_KTILES) s = ktiles / CONV_MIN_KTILES;
+    if (s > CONV_MAX_SPLIT) s = CONV_MAX_SPLIT;
+    if (s < 1) s = 1;
+    const long long per = ktiles ? (ktiles + s - 1) / s : 1;
+    return ConvSplit{ktiles ? (int)((ktiles + per - 1) / per) : 1, per};
+}
+// db's slabs: a function of B H W only
+int conv_db_split(long long M) {
+    const long long s = (M + CONV_DB_ROWS - 1) / CONV_DB_ROWS;
+    return s < 1 ? 1 : (s > CONV_DB_MAX ? CONV_DB_MAX : (int)s);
+}
+
+struct ConvWs { long long wp, part, dbpart, total; };           // byte offsets of the packed weight, the dw partials and the db partials
+ConvWs conv_ws(long long M, int Cin, int Cout, int dtype) {
+    ConvWs w;
+    const long long n = (long long)Cout * Cin;
+    w.wp = 0;
+    w.part = align16(9 * n * (dtype == MOGE_FP16 ? 2 : 4));
+    w.dbpart = w.part + 4LL * conv_split(M, Cin, Cout, dtype).parts * 9 * n;
+    w.total = w.dbpart + align16(4LL * conv_db_split(M) * Cout);
+    return w;
+}
+
+int check_sizes(const char* fn, int dtype, int B, int H, int W, int Cin, int Cout) {
+    if (dtype != MOGE_FP32 && dtype != MOGE_FP16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: unknown dtype %d (MOGE_FP32 or MOGE_FP16)", fn, dtype);
+    const int ch = chunk_of(dtype);
+    if (B < 0) return moge_internal_fail(MOGE_ERR_INVALID, "%s: B < 0", fn);
+    if (H < 1) return moge_internal_fail(MOGE_ERR_INVALID, "%s: H = %d < 1", fn, H);
+    if (W < 1) return moge_internal_fail(MOGE_ERR_INVALID, "%s: W = %d < 1", fn, W);
+    if (Cin < 1 || Cin % ch) return moge_internal_fail(MOGE_ERR_INVALID, "%s: Cin = %d is not a positive multiple of %d elements (16-byte vector accesses)", fn, Cin, ch);
+    if (Cout < 1 || Cout % ch) return moge_internal_fail(MOGE_ERR_INVALID, "%s: Cout = %d is not a positive multiple of %d elements (16-byte vector accesses)", fn, Cout, ch);
+    if ((long long)B * H * W > CONV_MAX_PIXELS || (long long)B * H > CONV_MAX_PIXELS) return moge_internal_fail(MOGE_ERR_INVALID, "%s: B H W exceeds 2^30 pixels", fn);
+    if ((long long)Cin * Cout > (1LL << 26)) return moge_internal_fail(MOGE_ERR_INVALID, "%s: Cin Cout exceeds 2^26", fn);
+    if (tiles((long long)B * H * W) * tiles(Cin > Cout ? Cin : Cout) > 0x7fffffffLL)
+        return moge_internal_fail(MOGE_ERR_INVALID, "%s: ceil(B H W / 128) ceil(max(Cin, Cout) / 128) exceeds the 2^31 - 1 workgroups of a grid", fn);
+    return 0;
+}
+
+// an activation (B, H, W, C) read or written in place on a dense pixel grid: 16-byte aligned, pixel stride a multiple of 16 bytes and at least C
+int check_pixels(const char* fn, const char* name, const char* ldname, const void* p, int64_t ld, int C, int dtype) {
+    if (!p) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is null", fn, name);
+    if ((uintptr_t)p % 16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is not 16-byte aligned", fn, name);
+    if (ld < C || ld % chunk_of(dtype))
+        return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s = %lld is not a multiple of %d elements (16-byte vector accesses) of at least the channel count %d", fn, ldname,
+                                  (long long)ld, chunk_of(dtype), C);
+    return 0;
+}
+int check_vector(const char* fn, const char* name, const void* p, bool required) {
+    if (!p && required) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is null", fn, name);
+    if ((uintptr_t)p % 16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is not 16-byte aligned", fn, name);
+    return 0;
+}
+
+template <typename T>
+void launch_repack(const void* w, void* wp, int Cin, int Cout, hipStream_t st) {
+    const int n = Cin * Cout;
+    hipLaunchKernelGGL(conv_repack_kernel<T>, dim3(blocks(n, 256)), dim3(256), 0, st, (const T*)w, (T*)wp, n);
+}
+
+template <typename T>
+void launch_forward(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, char* ws, int M, int H, int W, int Cin, int Cout, hipStream_t st) {
+    launch_repack<T>(w, ws, Cin, Cout, st);
+    hipLaunchKernelGGL((conv_kernel<T, false>), dim3((unsigned)(tiles(M) * tiles(Cout))), dim3(256), 0, st, (const T*)x, (long long)ldx, (const T*)ws, (const T*)bias, (T*)y,
+                       (long long)ldy, M, H, W, Cin, Cout, (int)tiles(Cout));
+}
+
+template <typename T>
+void launch_backward(const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, char* ws, const ConvWs& o, int M, int H,
+                     int W, int Cin, int Cout, int dtype, hipStream_t st) {
+    if (dx) {
+        launch_repack<T>(w, ws + o.wp, Cin, Cout, st);
+        hipLaunchKernelGGL((conv_kernel<T, true>), dim3((unsigned)(tiles(M) * tiles(Cin))), dim3(256), 0, st, (const T*)dy, (long long)lddy, (const T*)(ws + o.wp),
+                           (const T*)nullptr, (T*)dx, (long long)lddx, M, H, W, Cout, Cin, (int)tiles(Cin));
+    }
+    if (dw) {
+        constexpr int BK = LCPR * TT<T>::CH;
+        const ConvSplit sp = conv_split(M, Cin, Cout, dtype);
+        const int split = sp.parts, kper = (int)sp.per * BK;          // pixels of a part
+        float* part = (float*)(ws + o.part);
+        hipLaunchKernelGGL(conv_wgrad_kernel<T>, dim3((unsigned)(tiles(Cout) * tiles(Cin)), 9, (unsigned)split), dim3(256), 0, st, (const T*)dy, (long long)lddy, (const T*)x,
+                           (long long)ldx, part, M, H, W, Cout, Cin, kper, (int)tiles(Cin));
+        hipLaunchKernelGGL(conv_reduce_kernel<T>, dim3(blocks((int64_t)Cout * Cin, 256)), dim3(256), 0, st, (const float*)part, (T*)dw, Cout * Cin, split);
+    }
+    if (db) {
+        const int S = conv_db_split(M);
+        const int rows = (M + S - 1) / S;
+        float* part = (float*)(ws + o.dbpart);
+        hipLaunchKernelGGL(conv_colsum_kernel<T>, dim3(blocks(Cout, 8 * TT<T>::CH), (unsigned)S), dim3(256), 0, st, (const T*)dy, (long long)lddy, part, M, Cout, rows);
+        hipLaunchKernelGGL(conv_colsum_reduce_kernel<T>, dim3(blocks(Cout, 256)), dim3(256), 0, st, (const float*)part, (T*)db, Cout, S);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int moge_conv3x3_workspace(int B, int H, int W, int Cin, int Cout, int dtype, int64_t* forward_bytes, int64_t* backward_bytes) {
+    static const char* fn = "moge_conv3x3_workspace";
+    if (!forward_bytes) return moge_internal_fail(MOGE_ERR_INVALID, "%s: forward_bytes is null", fn);
+    if (!backward_bytes) return moge_internal_fail(MOGE_ERR_INVALID, "%s: backward_bytes is null", fn);
+    *forward_bytes = *backward_bytes = 0;
+    if (int e = check_sizes(fn, dtype, B, H, W, Cin, Cout)) return e;
+    const ConvWs o = conv_ws((long long)B * H * W, Cin, Cout, dtype);
+    *forward_bytes = o.part;
+    *backward_bytes = o.total;
+    return 0;
+}
+
+int moge_conv3x3_forward(int dtype, const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, int B, int H, int W, int Cin, int Cout, void* workspace,
+                         void* stream) {
+    static const char* fn = "moge_conv3x3_forward";
+    if (int e = check_sizes(fn, dtype, B, H, W, Cin, Cout)) return e;
+    if (B == 0) return 0;
+    if (int e = check_pixels(fn, "x", "ldx", x, ldx, Cin, dtype)) return e;
+    if (int e = check_vector(fn, "w", w, true)) return e;
+    if (int e = check_vector(fn, "bias", bias, false)) return e;
+    if (int e = check_pixels(fn, "y", "ldy", y, ldy, Cout, dtype)) return e;
+    if (int e = check_vector(fn, "workspace", workspace, true)) return e;
+    if (dtype == MOGE_FP16) launch_forward<f16>(x, ldx, w, bias, y, ldy, (char*)workspace, B * H * W, H, W, Cin, Cout, (hipStream_t)stream);
+    else launch_forward<float>(x, ldx, w, bias, y, ldy, (char*)workspace, B * H * W, H, W, Cin, Cout, (hipStream_t)stream);
+    return launched("moge_conv3x3_forward: launch failed");
+}
+
+int moge_conv3x3_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, void* workspace, int B,
+                          int H, int W, int Cin, int Cout, void* stream) {
+    static const char* fn = "moge_conv3x3_backward";
+    if (int e = check_sizes(fn, dtype, B, H, W, Cin, Cout)) return e;
+    if (B == 0 || (!dx && !dw && !db)) return 0;
+    if (int e = check_pixels(fn, "dy", "lddy", dy, lddy, Cout, dtype)) return e;
+    if (dx) {
+        if (int e = check_vector(fn, "w", w, true)) return e;
+        if (int e = check_pixels(fn, "dx", "lddx", dx, lddx, Cin, dtype)) return e;
+    }
+    if (dw) {
+        if (int e = check_pixels(fn, "x", "ldx", x, ldx, Cin, dtype)) return e;
+        if (int e = check_vector(fn, "dw", dw, true)) return e;
+    }
+    if (int e = check_vector(fn, "db", db, false)) return e;
+    if (int e = check_vector(fn, "workspace", workspace, true)) return e;
+    const int M = B * H * W;
+    const ConvWs o = conv_ws(M, Cin, Cout, dtype);
+    if (dtype == MOGE_FP16) launch_backward<f16>(x, ldx, w, dy, lddy, dx, lddx, dw, db, (char*)workspace, o, M, H, W, Cin, Cout, dtype, (hipStream_t)stream);
+    else launch_backward<float>(x, ldx, w, dy, lddy, dx, lddx, dw, db, (char*)workspace, o, M, H, W, Cin, Cout, dtype, (hipStream_t)stream);
+    return launched("moge_conv3x3_backward: launch failed");
+}
+
+}  // extern "C"

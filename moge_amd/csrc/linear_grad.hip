@@ -20,48 +20,6 @@
 
 namespace {
 
-constexpr int LT = 128;              // tile edge of C
-constexpr int LCPR = 8;              // chunks per K tile
-
-// The images here are 128 rows tall, and a transposed tile arrives with the lanes of a wave 8 (fp16) or 4 (fp32) rows apart: under the swizzle of common.h
-// alone (bits 1-3 of the row) their element stores fall on 4 of the 32 banks.  The chunk index is therefore XORed with bits 4-6 of the row as well, which
-// spreads those stores over 16 banks and is constant over the 16 consecutive rows a ds_read_b128 group reads, so the reads stay conflict-free.
-__device__ __forceinline__ int lin_x(int row) { return (row >> 4) & 7; }
-
-// 128 rows x LCPR chunks of one operand for the K tile at k0, as 4 chunks per thread.  TR false: p is [row][k], rows clamped, chunks past kend zero.
-// TR true: p is [k][row]; a chunk past kend or past the rows is zero (the row count is a multiple of the chunk).
-template <typename T, bool TR>
-__device__ __forceinline__ void lin_load(u32x4 (&r)[4], const T* __restrict__ p, long long ld, int row0, int rows, int k0, int kend, int tid) {
-    constexpr int CH = TT<T>::CH;
-    constexpr int RC = LT / CH;      // row chunks of a transposed tile row
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int cq = tid + i * 256;
-        r[i] = u32x4{0u, 0u, 0u, 0u};
-        if (!TR) {
-            const int row = cq / LCPR, c = cq - row * LCPR;
-            int g = row0 + row;
-            g = g < rows ? g : rows - 1;
-            const int k = k0 + c * CH;
-            if (k < kend) r[i] = ldg16(p + g * ld + k);
-        } else {
-            const int kk = cq / RC, rc = cq - kk * RC;
-            const int k = k0 + kk, g = row0 + rc * CH;
-            if (k < kend && g < rows) r[i] = ldg16(p + k * ld + g);
-        }
-    }
-}
-template <typename T, bool TR>
-__device__ __forceinline__ void lin_stage(char* img, const u32x4 (&r)[4], int tid) {
-    constexpr int RC = LT / TT<T>::CH;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int cq = tid + i * 256;
-        if (!TR) lds_put<LCPR>(img, cq / LCPR, (cq % LCPR) ^ lin_x(cq / LCPR), r[i]);
-        else lds_put_transposed<T, LCPR>(img, (cq / RC) ^ (lin_x((cq % RC) * TT<T>::CH) * TT<T>::CH), cq % RC, r[i]);      // the CH rows of a chunk share lin_x
-    }
-}
-
 // C (I, J) = A B^T over the contraction range [z kper, min(Kc, (z + 1) kper)), z = blockIdx.z; C += z * zstride (the split's fp32 partials)
 template <typename T, typename TO, bool TA, bool TB>
 __global__ __launch_bounds__(256) void linear_kernel(const T* __restrict__ A, long long lda, const T* __restrict__ B, long long ldb, const T* __restrict__ bias,
