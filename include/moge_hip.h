@@ -866,6 +866,35 @@ int moge_conv3x3_forward(int dtype, const void* x, int64_t ldx, const void* w, c
 int moge_conv3x3_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, void* workspace, int B,
                           int H, int W, int Cin, int Cout, void* stream);
 
+/* ---- trainable ConvTranspose2d(kernel 2, stride 2) of the decoder's conv_transpose resamplers and its gradients (python mirror moge_amd/convt.py,
+ * csrc/convt_grad.hip) ---------------------------------------------------------------------------------------------------
+ *   y [b, 2p+i, 2q+j, o] = bias[o] + sum_c x[b,p,q,c] w[c,o,i,j]                 i, j in {0, 1}
+ *   dx[b,p,q,c]          = sum_{i,j} sum_o dy[b, 2p+i, 2q+j, o] w[c,o,i,j]
+ *   dw[c,o,i,j]          = sum_{b,p,q} x[b,p,q,c] dy[b, 2p+i, 2q+j, o]           db[o] = sum over the 4 B H W pixels of dy[., ., ., o]
+ * The conventions are those of moge_conv3x3_*: stateless, queued on `stream`, nothing waits; dtype MOGE_FP32 or MOGE_FP16 is the storage type of every
+ * tensor (bias included), every sum is fp32 and a result is rounded once.  B, H, W are the INPUT grid: x and dx are NHWC (B, H, W, Cin), y and dy
+ * (B, 2H, 2W, Cout), each on a dense pixel grid and read or written in place through its pixel stride ld* (elements): pointer 16-byte aligned, ld a
+ * multiple of 16 bytes (8 fp16 / 4 fp32 elements) and at least C.  w and dw are torch's contiguous (Cin, Cout, 2, 2), bias and db (Cout), all 16-byte
+ * aligned.  Nothing outside [0, pixels) x [0, C) of any tensor is addressed.
+ * Cin, Cout: positive multiples of 16 bytes; H, W >= 1; B >= 0 (B = 0 is no work and no error, whatever the pointers).
+ * workspace: 16-byte aligned, of the size moge_convt2x2_workspace gives for the call; its contents need not survive from one call to the next.
+ *   forward_bytes  = the weight repacked to [tap][Cout][Cin] = 4 Cin Cout elements, rounded up to 16 bytes
+ *   backward_bytes = forward_bytes + 4 * S * 4 Cin Cout (the fp32 partials of dw) + 4 * D * Cout rounded up to 16 (those of db), with
+ *     S = ceil(K / ceil(K / S0)), K = ceil(B H W / T) K tiles of T = 64 (fp16) / 32 (fp32) pixels, S0 = max(1, min(512 / (4 ceil(Cin / 128) ceil(Cout / 128)), K / 8, 64)),
+ *     D = max(1, min(ceil(4 B H W / 512), 256))
+ * No atomics: the partials are added in split order, so two calls give the same bits; an image of y and of dx depends on its own image only.
+ * Limits: 4 B H W <= 2^30 (the pixels of the (2H, 2W) grid), Cin Cout <= 2^24, ceil(B H W / 128) ceil(max(Cin, 4 Cout) / 128) <= 2^31 - 1.  Bad arguments ->
+ * MOGE_ERR_INVALID with a message naming the function and the argument, before anything is launched.
+ * A 1x1 convolution has no entry of its own: on NHWC pixels it is moge_linear_* with M = B H W and the pixel stride as leading dimension. */
+int moge_convt2x2_workspace(int B, int H, int W, int Cin, int Cout, int dtype, int64_t* forward_bytes, int64_t* backward_bytes);
+/* bias may be NULL.  Two launches: the repack and the product. */
+int moge_convt2x2_forward(int dtype, const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, int B, int H, int W, int Cin, int Cout, void* workspace,
+                          void* stream);
+/* dx (B, H, W, Cin), dw (Cin, Cout, 2, 2), db (Cout): a NULL output is not computed and costs no launch (x is read for dw only, w for dx only).  Two
+ * launches for each output that is asked for. */
+int moge_convt2x2_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, void* workspace, int B,
+                           int H, int W, int Cin, int Cout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

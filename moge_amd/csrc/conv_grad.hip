@@ -63,54 +63,6 @@ __device__ __forceinline__ bool range_hits(long long m0, long long m1, int n, bo
     return (m0 + o + n - 1) / n * n <= m1 + o;
 }
 
-// the 2 x 2 mma_step tiles of a wave over one staged K tile (linear_kernel's loop)
-template <typename T>
-__device__ __forceinline__ void conv_mma(f32x16 (&acc)[2][2], const char* sA, const char* sB, int wi, int wj, int l31, int hi) {
-#pragma unroll
-    for (int s = 0; s < LCPR / 2; s++) {
-        u32x4 fa[2], fb[2];
-#pragma unroll
-        for (int a = 0; a < 2; a++) fa[a] = lds_chunk<LCPR>(sA, wi + a * 32 + l31, (2 * s + hi) ^ lin_x(wi + a * 32 + l31));
-#pragma unroll
-        for (int b = 0; b < 2; b++) fb[b] = lds_chunk<LCPR>(sB, wj + b * 32 + l31, (2 * s + hi) ^ lin_x(wj + b * 32 + l31));
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int b = 0; b < 2; b++) mma_step<T>(acc[a][b], fb[b], fa[a]);
-    }
-}
-
-__device__ __forceinline__ void conv_zero(f32x16 (&acc)[2][2]) {
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
-}
-
-// the row of C on the lane, its columns in the registers: four consecutive columns per store (linear_kernel's epilogue)
-template <typename TO, typename TB>
-__device__ __forceinline__ void conv_store(const f32x16 (&acc)[2][2], TO* __restrict__ C, long long ldc, const TB* __restrict__ bias, int i0, int I, int j0, int J, int wi, int wj,
-                                           int l31, int hi) {
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-        const int i = i0 + wi + a * 32 + l31;
-        if (i >= I) continue;
-        TO* crow = C + i * ldc;
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; g4++) {
-                const int j = j0 + wj + b * 32 + 8 * g4 + 4 * hi;
-                if (j >= J) continue;                                   // J is a multiple of 4: a group of four is inside or outside
-                float bv[4] = {0.f, 0.f, 0.f, 0.f};
-                if (bias) load4(bias + j, bv);
-                store4(crow + j, acc[a][b][4 * g4] + bv[0], acc[a][b][4 * g4 + 1] + bv[1], acc[a][b][4 * g4 + 2] + bv[2], acc[a][b][4 * g4 + 3] + bv[3]);
-            }
-    }
-}
-
 // forward (DG false): C = y, A = x, Kc = Cin, J = Cout.  dgrad (DG true): C = dx, A = dy, Kc = Cout, J = Cin.  wp: [tap][Cout][Cin].  M = B H W pixels.
 template <typename T, bool DG>
 __global__ __launch_bounds__(256) void conv_kernel(const T* __restrict__ A, long long lda, const T* __restrict__ wp, const T* __restrict__ bias, T* __restrict__ C,
@@ -268,48 +220,6 @@ __global__ __launch_bounds__(256) void conv_reduce_kernel(const float* __restric
         for (int z = 1; z < S; z++) v += part[((long long)z * 9 + tap) * n + e];
         dw[(long long)e * 9 + tap] = (T)v;
     }
-}
-
-// part[z][o] = sum of dy[m][o] over the slab of rows [z rows, min(M, (z + 1) rows)): a workgroup takes 8 column chunks, 32 threads per chunk sum the
-// rows r, r + 32, ... of the slab in that order, then the 32 partials are added in the order r = 0 ... 31 (lin_colsum_kernel's order, per slab)
-template <typename T>
-__global__ __launch_bounds__(256) void conv_colsum_kernel(const T* __restrict__ dy, long long lddy, float* __restrict__ part, int M, int N, int rows) {
-    constexpr int CH = TT<T>::CH;
-    __shared__ float sum[32][8 * CH + 1];
-    const int tid = threadIdx.x, c = tid & 7, r = tid >> 3;
-    const int n = (blockIdx.x * 8 + c) * CH;
-    const int mbeg = blockIdx.y * rows;
-    const int mend = M - mbeg < rows ? M : mbeg + rows;
-    float s[CH];
-#pragma unroll
-    for (int e = 0; e < CH; e++) s[e] = 0.f;
-    if (n < N)
-        for (int m = mbeg + r; m < mend; m += 32) {
-            const typename Vec<T>::type v = __builtin_bit_cast(typename Vec<T>::type, ldg16(dy + m * lddy + n));
-#pragma unroll
-            for (int e = 0; e < CH; e++) s[e] += (float)v[e];
-        }
-#pragma unroll
-    for (int e = 0; e < CH; e++) sum[r][c * CH + e] = s[e];
-    __syncthreads();
-    if (tid < 8 * CH) {
-        const int col = blockIdx.x * 8 * CH + tid;
-        if (col < N) {
-            float v = sum[0][tid];
-            for (int i = 1; i < 32; i++) v += sum[i][tid];
-            part[(long long)blockIdx.y * N + col] = v;
-        }
-    }
-}
-
-// db[o] = the slab sums added in slab order, rounded once
-template <typename T>
-__global__ __launch_bounds__(256) void conv_colsum_reduce_kernel(const float* __restrict__ part, T* __restrict__ db, int N, int S) {
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o >= N) return;
-    float v = part[o];
-    for (int z = 1; z < S; z++) v += part[(long long)z * N + o];
-    db[o] = (T)v;
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
