@@ -19,12 +19,13 @@
 // combination with a border kind runs only in workgroups whose 128 pixels touch that border (decided from the tile's pixel range, wave-uniform).
 //
 // wgrad: grid = tiles of (Cout, Cin) x 9 taps x conv_split; every workgroup writes an fp32 partial [split][tap][Cout][Cin] to the workspace and
-// conv_reduce_kernel adds them in split order into torch's (Cout, Cin, 3, 3) layout, rounding once.  db: fp32 column sums of slabs of rows, added in slab
+// lin_tap_reduce_kernel<T, 9> (lds_image.h) adds them in split order into torch's (Cout, Cin, 3, 3) layout, rounding once.  db: fp32 column sums of slabs of rows, added in slab
 // order.  Both splits are functions of the sizes only.  No atomics anywhere: two calls give the same bits.
+// The host half - checks, splits, workspace layout, the db launch, the entry points' bodies - is grad_host.h's, shared with convt_grad.hip; this file
+// gives it the traits struct Conv3x3 (constants, limits, the three launches).
 // Tails: as linear_grad.hip - a pixel row past B H W is clamped where it is a row of C and zero where it is the contraction index, a chunk past the
 // contraction range is zero, nothing outside [0, B H W) x [0, C) is addressed, stores are guarded.  Offsets are 64-bit.
-#include "common.h"
-#include "lds_image.h"
+#include "grad_host.h"
 
 namespace {
 
@@ -73,11 +74,8 @@ __global__ __launch_bounds__(256) void conv_kernel(const T* __restrict__ A, long
     __shared__ __attribute__((aligned(16))) char sA[LT * LCPR * 16];      // [pixel][k]
     __shared__ __attribute__((aligned(16))) char sB[LT * LCPR * 16];      // [j][k]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hi = lane >> 5, l31 = lane & 31;
-    const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
-    const int i0 = ti * LT, j0 = tj * LT;
-    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+    const LinTile wg = lin_tile(tiles_j);
+    const int tid = wg.tid, hi = wg.hi, l31 = wg.l31, i0 = wg.i0, j0 = wg.j0, wi = wg.wi, wj = wg.wj;
 
     // the steps this workgroup runs: all of the forward's 9; of the dgrad's 25, a border kind only where the tile's pixels touch that border
     unsigned mask = 0x1ffu;
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(256) void conv_kernel(const T* __restrict__ A, long
     const long long wtap = (long long)Kc * J;
 
     f32x16 acc[2][2];
-    conv_zero(acc);
+    lin_zero(acc);
 
     u32x4 ra[4], rb[4];
     int opt = 0, k0 = 0;                                                  // step 0 is in every mask
@@ -127,12 +125,12 @@ __global__ __launch_bounds__(256) void conv_kernel(const T* __restrict__ A, long
             conv_load<T, DG>(ra, A, lda, m, P, Q, H, W, nopt, nk + kc, Kc);
             lin_load<T, DG>(rb, wp + (axis_tap<DG>(a) * 3 + axis_tap<DG>(b)) * wtap, DG ? J : Kc, j0, J, nk, Kc, tid);
         }
-        conv_mma<T>(acc, sA, sB, wi, wj, l31, hi);
+        lin_mma<T>(acc, sA, sB, wi, wj, l31, hi);
         if (nopt < 0) break;
         opt = nopt;
         k0 = nk;
     }
-    conv_store<T, T>(acc, C, ldc, bias, i0, M, j0, J, wi, wj, l31, hi);
+    lin_store<T, T>(acc, C, ldc, bias, i0, M, j0, J, wi, wj, l31, hi);
 }
 
 // part[z][tap][Cout][Cin] = sum over the pixels [z kper, min(M, (z + 1) kper)) of dy[m][o] x[src(m, tap)][i]; tap = blockIdx.y, z = blockIdx.z
@@ -145,11 +143,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const T* __restrict__ d
     __shared__ __attribute__((aligned(16))) char sA[LT * LCPR * 16];      // [o][pixel]
     __shared__ __attribute__((aligned(16))) char sB[LT * LCPR * 16];      // [i][pixel]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hi = lane >> 5, l31 = lane & 31;
-    const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
-    const int i0 = ti * LT, j0 = tj * LT;
-    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+    const LinTile wg = lin_tile(tiles_j);
+    const int tid = wg.tid, hi = wg.hi, l31 = wg.l31, i0 = wg.i0, j0 = wg.j0, wi = wg.wi, wj = wg.wj;
     const int tap = blockIdx.y, s = tap / 3 - 1, t = tap - (tap / 3) * 3 - 1;
     const int kbeg = blockIdx.z * kper;
     const int kend = M - kbeg < kper ? M : kbeg + kper;
@@ -181,7 +176,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const T* __restrict__ d
     };
 
     f32x16 acc[2][2];
-    conv_zero(acc);
+    lin_zero(acc);
 
     u32x4 ra[4], rb[4];
     lin_load<T, true>(ra, dy, lddy, i0, Cout, kbeg, kend, tid);
@@ -195,9 +190,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const T* __restrict__ d
             lin_load<T, true>(ra, dy, lddy, i0, Cout, k0 + BK, kend, tid);
             load_x(rb, k0 + BK);
         }
-        conv_mma<T>(acc, sA, sB, wi, wj, l31, hi);
+        lin_mma<T>(acc, sA, sB, wi, wj, l31, hi);
     }
-    conv_store<float, float>(acc, part + ((long long)blockIdx.z * 9 + tap) * Cout * Cin, Cin, nullptr, i0, Cout, j0, Cin, wi, wj, l31, hi);
+    lin_store<float, float>(acc, part + ((long long)blockIdx.z * 9 + tap) * Cout * Cin, Cin, nullptr, i0, Cout, j0, Cin, wi, wj, l31, hi);
 }
 
 // wp[tap][o][i] = w[o][i][tap]: an exact copy, one thread per (o, i)
@@ -209,182 +204,59 @@ __global__ __launch_bounds__(256) void conv_repack_kernel(const T* __restrict__ 
     for (int tap = 0; tap < 9; tap++) wp[(long long)tap * n + e] = w[(long long)e * 9 + tap];
 }
 
-// dw[o][i][tap] = the S partials added in split order, rounded once; one thread per (o, i)
-template <typename T>
-__global__ __launch_bounds__(256) void conv_reduce_kernel(const float* __restrict__ part, T* __restrict__ dw, int n, int S) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-#pragma unroll
-    for (int tap = 0; tap < 9; tap++) {
-        float v = part[(long long)tap * n + e];
-        for (int z = 1; z < S; z++) v += part[((long long)z * 9 + tap) * n + e];
-        dw[(long long)e * 9 + tap] = (T)v;
+// ---- host side: the constants and launches of this conv; the entry points' bodies are grad_host.h's ---------------------------------
+struct Conv3x3 {
+    static constexpr const char* NAME = "moge_conv3x3";
+    static constexpr int TAPS = 9, UP = 1, COLS = 1;
+    static constexpr int FILL = 512;             // workgroups wgrad aims for: a constant, not the device's CU count, so that the bits do not depend on the device
+    static constexpr int MAX_SPLIT = 64;
+    static constexpr int MIN_KTILES = 8;         // K tiles (of 64 fp16 / 32 fp32 pixels) a split keeps at least
+    static constexpr int DB_ROWS = 4096;         // pixels of a db slab at the least
+    static constexpr int DB_MAX = 256;           // slabs at the most
+    static constexpr long long MAX_WEIGHT = 1LL << 26;
+    static constexpr const char* PIXELS_MSG = "B H W exceeds 2^30 pixels";
+    static constexpr const char* WEIGHT_MSG = "Cin Cout exceeds 2^26";
+    static constexpr const char* GRID_MSG = "ceil(B H W / 128) ceil(max(Cin, Cout) / 128) exceeds the 2^31 - 1 workgroups of a grid";
+
+    template <typename T> static void repack(const void* w, void* wp, int Cin, int Cout, hipStream_t st) {
+        const int n = Cin * Cout;
+        hipLaunchKernelGGL(conv_repack_kernel<T>, dim3(blocks(n, 256)), dim3(256), 0, st, (const T*)w, (T*)wp, n);
     }
-}
-
-// ---- host side -------------------------------------------------------------------------------------------------------------------
-constexpr int CONV_MAX_SPLIT = 64;
-constexpr int CONV_FILL = 512;             // workgroups wgrad aims for: a constant, not the device's CU count, so that the bits do not depend on the device
-constexpr int CONV_MIN_KTILES = 8;         // K tiles (of 64 fp16 / 32 fp32 pixels) a split keeps at least
-constexpr int CONV_DB_ROWS = 4096;         // pixels of a db slab at the least
-constexpr int CONV_DB_MAX = 256;           // slabs at the most
-constexpr long long CONV_MAX_PIXELS = 1LL << 30;
-
-inline long long tiles(long long n) { return (n + LT - 1) / LT; }
-inline int chunk_of(int dtype) { return dtype == MOGE_FP16 ? 8 : 4; }
-inline long long align16(long long n) { return (n + 15) / 16 * 16; }
-
-// wgrad's split of the pixels: a function of (B H W, Cin, Cout, dtype) only.  `per` K tiles to a part, `parts` parts that have work (the last one takes
-// what is left); the workspace query and the launch both read this one result.
-struct ConvSplit { int parts; long long per; };
-ConvSplit conv_split(long long M, int Cin, int Cout, int dtype) {
-    const long long t = 9 * tiles(Cout) * tiles(Cin);
-    const long long ktiles = (M + LCPR * chunk_of(dtype) - 1) / (LCPR * chunk_of(dtype));
-    long long s = CONV_FILL / t;
-    if (s > ktiles / CONV_MIN_KTILES) s = ktiles / CONV_MIN_KTILES;
-    if (s > CONV_MAX_SPLIT) s = CONV_MAX_SPLIT;
-    if (s < 1) s = 1;
-    const long long per = ktiles ? (ktiles + s - 1) / s : 1;
-    return ConvSplit{ktiles ? (int)((ktiles + per - 1) / per) : 1, per};
-}
-// db's slabs: a function of B H W only
-int conv_db_split(long long M) {
-    const long long s = (M + CONV_DB_ROWS - 1) / CONV_DB_ROWS;
-    return s < 1 ? 1 : (s > CONV_DB_MAX ? CONV_DB_MAX : (int)s);
-}
-
-struct ConvWs { long long wp, part, dbpart, total; };           // byte offsets of the packed weight, the dw partials and the db partials
-ConvWs conv_ws(long long M, int Cin, int Cout, int dtype) {
-    ConvWs w;
-    const long long n = (long long)Cout * Cin;
-    w.wp = 0;
-    w.part = align16(9 * n * (dtype == MOGE_FP16 ? 2 : 4));
-    w.dbpart = w.part + 4LL * conv_split(M, Cin, Cout, dtype).parts * 9 * n;
-    w.total = w.dbpart + align16(4LL * conv_db_split(M) * Cout);
-    return w;
-}
-
-int check_sizes(const char* fn, int dtype, int B, int H, int W, int Cin, int Cout) {
-    if (dtype != MOGE_FP32 && dtype != MOGE_FP16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: unknown dtype %d (MOGE_FP32 or MOGE_FP16)", fn, dtype);
-    const int ch = chunk_of(dtype);
-    if (B < 0) return moge_internal_fail(MOGE_ERR_INVALID, "%s: B < 0", fn);
-    if (H < 1) return moge_internal_fail(MOGE_ERR_INVALID, "%s: H = %d < 1", fn, H);
-    if (W < 1) return moge_internal_fail(MOGE_ERR_INVALID, "%s: W = %d < 1", fn, W);
-    if (Cin < 1 || Cin % ch) return moge_internal_fail(MOGE_ERR_INVALID, "%s: Cin = %d is not a positive multiple of %d elements (16-byte vector accesses)", fn, Cin, ch);
-    if (Cout < 1 || Cout % ch) return moge_internal_fail(MOGE_ERR_INVALID, "%s: Cout = %d is not a positive multiple of %d elements (16-byte vector accesses)", fn, Cout, ch);
-    if ((long long)B * H * W > CONV_MAX_PIXELS || (long long)B * H > CONV_MAX_PIXELS) return moge_internal_fail(MOGE_ERR_INVALID, "%s: B H W exceeds 2^30 pixels", fn);
-    if ((long long)Cin * Cout > (1LL << 26)) return moge_internal_fail(MOGE_ERR_INVALID, "%s: Cin Cout exceeds 2^26", fn);
-    if (tiles((long long)B * H * W) * tiles(Cin > Cout ? Cin : Cout) > 0x7fffffffLL)
-        return moge_internal_fail(MOGE_ERR_INVALID, "%s: ceil(B H W / 128) ceil(max(Cin, Cout) / 128) exceeds the 2^31 - 1 workgroups of a grid", fn);
-    return 0;
-}
-
-// an activation (B, H, W, C) read or written in place on a dense pixel grid: 16-byte aligned, pixel stride a multiple of 16 bytes and at least C
-int check_pixels(const char* fn, const char* name, const char* ldname, const void* p, int64_t ld, int C, int dtype) {
-    if (!p) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is null", fn, name);
-    if ((uintptr_t)p % 16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is not 16-byte aligned", fn, name);
-    if (ld < C || ld % chunk_of(dtype))
-        return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s = %lld is not a multiple of %d elements (16-byte vector accesses) of at least the channel count %d", fn, ldname,
-                                  (long long)ld, chunk_of(dtype), C);
-    return 0;
-}
-int check_vector(const char* fn, const char* name, const void* p, bool required) {
-    if (!p && required) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is null", fn, name);
-    if ((uintptr_t)p % 16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is not 16-byte aligned", fn, name);
-    return 0;
-}
-
-template <typename T>
-void launch_repack(const void* w, void* wp, int Cin, int Cout, hipStream_t st) {
-    const int n = Cin * Cout;
-    hipLaunchKernelGGL(conv_repack_kernel<T>, dim3(blocks(n, 256)), dim3(256), 0, st, (const T*)w, (T*)wp, n);
-}
-
-template <typename T>
-void launch_forward(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, char* ws, int M, int H, int W, int Cin, int Cout, hipStream_t st) {
-    launch_repack<T>(w, ws, Cin, Cout, st);
-    hipLaunchKernelGGL((conv_kernel<T, false>), dim3((unsigned)(tiles(M) * tiles(Cout))), dim3(256), 0, st, (const T*)x, (long long)ldx, (const T*)ws, (const T*)bias, (T*)y,
-                       (long long)ldy, M, H, W, Cin, Cout, (int)tiles(Cout));
-}
-
-template <typename T>
-void launch_backward(const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, char* ws, const ConvWs& o, int M, int H,
-                     int W, int Cin, int Cout, int dtype, hipStream_t st) {
-    if (dx) {
-        launch_repack<T>(w, ws + o.wp, Cin, Cout, st);
-        hipLaunchKernelGGL((conv_kernel<T, true>), dim3((unsigned)(tiles(M) * tiles(Cin))), dim3(256), 0, st, (const T*)dy, (long long)lddy, (const T*)(ws + o.wp),
-                           (const T*)nullptr, (T*)dx, (long long)lddx, M, H, W, Cout, Cin, (int)tiles(Cin));
+    template <typename T>
+    static void forward(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, void* wp, int M, int H, int W, int Cin, int Cout, hipStream_t st) {
+        repack<T>(w, wp, Cin, Cout, st);
+        hipLaunchKernelGGL((conv_kernel<T, false>), dim3((unsigned)(tiles(M) * tiles(Cout))), dim3(256), 0, st, (const T*)x, (long long)ldx, (const T*)wp, (const T*)bias, (T*)y,
+                           (long long)ldy, M, H, W, Cin, Cout, (int)tiles(Cout));
     }
-    if (dw) {
-        constexpr int BK = LCPR * TT<T>::CH;
-        const ConvSplit sp = conv_split(M, Cin, Cout, dtype);
-        const int split = sp.parts, kper = (int)sp.per * BK;          // pixels of a part
-        float* part = (float*)(ws + o.part);
+    template <typename T>
+    static void dgrad(const void* dy, int64_t lddy, const void* w, void* wp, void* dx, int64_t lddx, int M, int H, int W, int Cin, int Cout, hipStream_t st) {
+        repack<T>(w, wp, Cin, Cout, st);
+        hipLaunchKernelGGL((conv_kernel<T, true>), dim3((unsigned)(tiles(M) * tiles(Cin))), dim3(256), 0, st, (const T*)dy, (long long)lddy, (const T*)wp, (const T*)nullptr,
+                           (T*)dx, (long long)lddx, M, H, W, Cout, Cin, (int)tiles(Cin));
+    }
+    template <typename T>
+    static void wgrad(const void* x, int64_t ldx, const void* dy, int64_t lddy, float* part, int M, int H, int W, int Cin, int Cout, int split, int kper, hipStream_t st) {
         hipLaunchKernelGGL(conv_wgrad_kernel<T>, dim3((unsigned)(tiles(Cout) * tiles(Cin)), 9, (unsigned)split), dim3(256), 0, st, (const T*)dy, (long long)lddy, (const T*)x,
                            (long long)ldx, part, M, H, W, Cout, Cin, kper, (int)tiles(Cin));
-        hipLaunchKernelGGL(conv_reduce_kernel<T>, dim3(blocks((int64_t)Cout * Cin, 256)), dim3(256), 0, st, (const float*)part, (T*)dw, Cout * Cin, split);
     }
-    if (db) {
-        const int S = conv_db_split(M);
-        const int rows = (M + S - 1) / S;
-        float* part = (float*)(ws + o.dbpart);
-        hipLaunchKernelGGL(conv_colsum_kernel<T>, dim3(blocks(Cout, 8 * TT<T>::CH), (unsigned)S), dim3(256), 0, st, (const T*)dy, (long long)lddy, part, M, Cout, rows);
-        hipLaunchKernelGGL(conv_colsum_reduce_kernel<T>, dim3(blocks(Cout, 256)), dim3(256), 0, st, (const float*)part, (T*)db, Cout, S);
-    }
-}
+};
 
 }  // namespace
 
 extern "C" {
 
 int moge_conv3x3_workspace(int B, int H, int W, int Cin, int Cout, int dtype, int64_t* forward_bytes, int64_t* backward_bytes) {
-    static const char* fn = "moge_conv3x3_workspace";
-    if (!forward_bytes) return moge_internal_fail(MOGE_ERR_INVALID, "%s: forward_bytes is null", fn);
-    if (!backward_bytes) return moge_internal_fail(MOGE_ERR_INVALID, "%s: backward_bytes is null", fn);
-    *forward_bytes = *backward_bytes = 0;
-    if (int e = check_sizes(fn, dtype, B, H, W, Cin, Cout)) return e;
-    const ConvWs o = conv_ws((long long)B * H * W, Cin, Cout, dtype);
-    *forward_bytes = o.part;
-    *backward_bytes = o.total;
-    return 0;
+    return conv_workspace<Conv3x3>(B, H, W, Cin, Cout, dtype, forward_bytes, backward_bytes);
 }
 
 int moge_conv3x3_forward(int dtype, const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, int B, int H, int W, int Cin, int Cout, void* workspace,
                          void* stream) {
-    static const char* fn = "moge_conv3x3_forward";
-    if (int e = check_sizes(fn, dtype, B, H, W, Cin, Cout)) return e;
-    if (B == 0) return 0;
-    if (int e = check_pixels(fn, "x", "ldx", x, ldx, Cin, dtype)) return e;
-    if (int e = check_vector(fn, "w", w, true)) return e;
-    if (int e = check_vector(fn, "bias", bias, false)) return e;
-    if (int e = check_pixels(fn, "y", "ldy", y, ldy, Cout, dtype)) return e;
-    if (int e = check_vector(fn, "workspace", workspace, true)) return e;
-    if (dtype == MOGE_FP16) launch_forward<f16>(x, ldx, w, bias, y, ldy, (char*)workspace, B * H * W, H, W, Cin, Cout, (hipStream_t)stream);
-    else launch_forward<float>(x, ldx, w, bias, y, ldy, (char*)workspace, B * H * W, H, W, Cin, Cout, (hipStream_t)stream);
-    return launched("moge_conv3x3_forward: launch failed");
+    return conv_forward<Conv3x3>(dtype, x, ldx, w, bias, y, ldy, B, H, W, Cin, Cout, workspace, stream);
 }
 
 int moge_conv3x3_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, void* workspace, int B,
                           int H, int W, int Cin, int Cout, void* stream) {
-    static const char* fn = "moge_conv3x3_backward";
-    if (int e = check_sizes(fn, dtype, B, H, W, Cin, Cout)) return e;
-    if (B == 0 || (!dx && !dw && !db)) return 0;
-    if (int e = check_pixels(fn, "dy", "lddy", dy, lddy, Cout, dtype)) return e;
-    if (dx) {
-        if (int e = check_vector(fn, "w", w, true)) return e;
-        if (int e = check_pixels(fn, "dx", "lddx", dx, lddx, Cin, dtype)) return e;
-    }
-    if (dw) {
-        if (int e = check_pixels(fn, "x", "ldx", x, ldx, Cin, dtype)) return e;
-        if (int e = check_vector(fn, "dw", dw, true)) return e;
-    }
-    if (int e = check_vector(fn, "db", db, false)) return e;
-    if (int e = check_vector(fn, "workspace", workspace, true)) return e;
-    const int M = B * H * W;
-    const ConvWs o = conv_ws(M, Cin, Cout, dtype);
-    if (dtype == MOGE_FP16) launch_backward<f16>(x, ldx, w, dy, lddy, dx, lddx, dw, db, (char*)workspace, o, M, H, W, Cin, Cout, dtype, (hipStream_t)stream);
-    else launch_backward<float>(x, ldx, w, dy, lddy, dx, lddx, dw, db, (char*)workspace, o, M, H, W, Cin, Cout, dtype, (hipStream_t)stream);
-    return launched("moge_conv3x3_backward: launch failed");
+    return conv_backward<Conv3x3>(dtype, x, ldx, w, dy, lddy, dx, lddx, dw, db, workspace, B, H, W, Cin, Cout, stream);
 }
 
 }  // extern "C"

@@ -15,13 +15,13 @@
 //     wgrad    A = x read as (Cin, pixels)  B = dy gathered, read as (Cout, pixels)  pixels, split  grid: tiles x 4 taps x S                    convt_wgrad_kernel
 // A chunk of 16 bytes and a group of four columns never straddle a tap, because Cout is a multiple of the chunk.  dgrad has no border and no mask: every
 // dx has exactly four source pixels, and its 4 Cout products go into one fp32 accumulator over one contraction range, so a K tile may hold two taps.
-// wgrad keeps x as the row operand so that a partial lies as [split][tap][Cin][Cout], the weight's own channel order: convt_reduce_kernel reads the
+// wgrad keeps x as the row operand so that a partial lies as [split][tap][Cin][Cout], the weight's own channel order: lin_tap_reduce_kernel<T, 4> (lds_image.h) reads the
 // partials and writes the four taps of a (c, o) contiguously, adding in split order and rounding once.  db: dy is a dense grid of 4 B H W rows, the slab
 // column sum of lds_image.h as it is.  Both splits are functions of the sizes and the dtype only.  No atomics anywhere: two calls give the same bits.
+// The host half is grad_host.h's, as in conv_grad.hip; this file gives it the traits struct ConvT2x2.
 // Tails: as linear_grad.hip - a pixel row past B H W is clamped where it is a row of C (not stored) and zero where it is the contraction index, a chunk
 // past the contraction range is zero, nothing outside [0, pixels) x [0, C) is addressed, stores are guarded.  Offsets are 64-bit.
-#include "common.h"
-#include "lds_image.h"
+#include "grad_host.h"
 
 namespace {
 
@@ -42,15 +42,12 @@ __global__ __launch_bounds__(256) void convt_kernel(const T* __restrict__ x, lon
     __shared__ __attribute__((aligned(16))) char sA[LT * LCPR * 16];      // [pixel][c]
     __shared__ __attribute__((aligned(16))) char sB[LT * LCPR * 16];      // [tap Cout + o][c]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hi = lane >> 5, l31 = lane & 31;
-    const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
-    const int i0 = ti * LT, j0 = tj * LT;
-    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+    const LinTile wg = lin_tile(tiles_j);
+    const int tid = wg.tid, hi = wg.hi, l31 = wg.l31, i0 = wg.i0, j0 = wg.j0, wi = wg.wi, wj = wg.wj;
     const int J = 4 * Cout;
 
     f32x16 acc[2][2];
-    conv_zero(acc);
+    lin_zero(acc);
 
     u32x4 ra[4], rb[4];
     lin_load<T, false>(ra, x, ldx, i0, M, 0, Cin, tid);
@@ -64,7 +61,7 @@ __global__ __launch_bounds__(256) void convt_kernel(const T* __restrict__ x, lon
             lin_load<T, false>(ra, x, ldx, i0, M, k0 + BK, Cin, tid);
             lin_load<T, false>(rb, wp, Cin, j0, J, k0 + BK, Cin, tid);
         }
-        conv_mma<T>(acc, sA, sB, wi, wj, l31, hi);
+        lin_mma<T>(acc, sA, sB, wi, wj, l31, hi);
     }
 #pragma unroll
     for (int a = 0; a < 2; a++) {
@@ -95,11 +92,8 @@ __global__ __launch_bounds__(256) void convt_dgrad_kernel(const T* __restrict__ 
     __shared__ __attribute__((aligned(16))) char sA[LT * LCPR * 16];      // [pixel][k]
     __shared__ __attribute__((aligned(16))) char sB[LT * LCPR * 16];      // [c][k]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hi = lane >> 5, l31 = lane & 31;
-    const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
-    const int i0 = ti * LT, j0 = tj * LT;
-    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+    const LinTile wg = lin_tile(tiles_j);
+    const int tid = wg.tid, hi = wg.hi, l31 = wg.l31, i0 = wg.i0, j0 = wg.j0, wi = wg.wi, wj = wg.wj;
     const int K = 4 * Cout;
 
     // the four pixel rows a thread loads in every K tile (the rows of lin_load<T, false>), and its chunk of the tile
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(256) void convt_dgrad_kernel(const T* __restrict__ 
     };
 
     f32x16 acc[2][2];
-    conv_zero(acc);
+    lin_zero(acc);
 
     u32x4 ra[4], rb[4];
     load_dy(ra, 0);
@@ -135,9 +129,9 @@ __global__ __launch_bounds__(256) void convt_dgrad_kernel(const T* __restrict__ 
             load_dy(ra, k0 + BK);
             lin_load<T, true>(rb, wp, Cin, j0, Cin, k0 + BK, K, tid);
         }
-        conv_mma<T>(acc, sA, sB, wi, wj, l31, hi);
+        lin_mma<T>(acc, sA, sB, wi, wj, l31, hi);
     }
-    conv_store<T, T>(acc, dx, lddx, nullptr, i0, M, j0, Cin, wi, wj, l31, hi);
+    lin_store<T, T>(acc, dx, lddx, nullptr, i0, M, j0, Cin, wi, wj, l31, hi);
 }
 
 // part[z][tap][Cin][Cout] = sum over the pixels m in [z kper, min(M, (z + 1) kper)) of x[m][c] dy[convt_hi(m) + tap][o]; tap = blockIdx.y, z = blockIdx.z
@@ -150,11 +144,8 @@ __global__ __launch_bounds__(256) void convt_wgrad_kernel(const T* __restrict__ 
     __shared__ __attribute__((aligned(16))) char sA[LT * LCPR * 16];      // [c][pixel]
     __shared__ __attribute__((aligned(16))) char sB[LT * LCPR * 16];      // [o][pixel]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hi = lane >> 5, l31 = lane & 31;
-    const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
-    const int i0 = ti * LT, j0 = tj * LT;
-    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+    const LinTile wg = lin_tile(tiles_j);
+    const int tid = wg.tid, hi = wg.hi, l31 = wg.l31, i0 = wg.i0, j0 = wg.j0, wi = wg.wi, wj = wg.wj;
     const int tap = blockIdx.y, d = convt_tap(tap, W);
     const int kbeg = blockIdx.z * kper;
     const int kend = M - kbeg < kper ? M : kbeg + kper;
@@ -170,7 +161,7 @@ __global__ __launch_bounds__(256) void convt_wgrad_kernel(const T* __restrict__ 
     };
 
     f32x16 acc[2][2];
-    conv_zero(acc);
+    lin_zero(acc);
 
     u32x4 ra[4], rb[4];
     lin_load<T, true>(ra, x, ldx, i0, Cin, kbeg, kend, tid);
@@ -184,9 +175,9 @@ __global__ __launch_bounds__(256) void convt_wgrad_kernel(const T* __restrict__ 
             lin_load<T, true>(ra, x, ldx, i0, Cin, k0 + BK, kend, tid);
             load_dy(rb, k0 + BK);
         }
-        conv_mma<T>(acc, sA, sB, wi, wj, l31, hi);
+        lin_mma<T>(acc, sA, sB, wi, wj, l31, hi);
     }
-    conv_store<float, float>(acc, part + ((long long)blockIdx.z * 4 + tap) * Cin * Cout, Cout, nullptr, i0, Cin, j0, Cout, wi, wj, l31, hi);
+    lin_store<float, float>(acc, part + ((long long)blockIdx.z * 4 + tap) * Cin * Cout, Cout, nullptr, i0, Cin, j0, Cout, wi, wj, l31, hi);
 }
 
 // wp[tap][o][c] = w[c][o][tap]: an exact copy, one thread per (o, c), the four taps of a (c, o) read as one vector
@@ -201,183 +192,58 @@ __global__ __launch_bounds__(256) void convt_repack_kernel(const T* __restrict__
     for (int tap = 0; tap < 4; tap++) wp[(long long)tap * n + e] = v[tap];
 }
 
-// dw[c][o][tap] = the S partials added in split order, rounded once; one thread per (c, o), its four taps stored as one vector
-template <typename T>
-__global__ __launch_bounds__(256) void convt_reduce_kernel(const float* __restrict__ part, T* __restrict__ dw, int n, int S) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-    float v[4];
-#pragma unroll
-    for (int tap = 0; tap < 4; tap++) {
-        v[tap] = part[(long long)tap * n + e];
-        for (int z = 1; z < S; z++) v[tap] += part[((long long)z * 4 + tap) * n + e];
+// ---- host side: the constants and launches of this conv; the entry points' bodies are grad_host.h's ---------------------------------
+struct ConvT2x2 {
+    static constexpr const char* NAME = "moge_convt2x2";
+    static constexpr int TAPS = 4, UP = 4, COLS = 4;      // the forward's columns are the (tap, o) pairs
+    static constexpr int FILL = 512;             // workgroups wgrad aims for: a constant, not the device's CU count, so that the bits do not depend on the device
+    static constexpr int MAX_SPLIT = 64;
+    static constexpr int MIN_KTILES = 8;         // K tiles (of 64 fp16 / 32 fp32 low-resolution pixels) a split keeps at least
+    static constexpr int DB_ROWS = 512;          // high-resolution pixels of a db slab at the least: 16 rows to each of a workgroup's 32 row threads
+    static constexpr int DB_MAX = 256;           // slabs at the most
+    static constexpr long long MAX_WEIGHT = 1LL << 24;
+    static constexpr const char* PIXELS_MSG = "4 B H W exceeds 2^30 pixels of the (2H, 2W) grid";
+    static constexpr const char* WEIGHT_MSG = "Cin Cout exceeds 2^24";
+    static constexpr const char* GRID_MSG = "ceil(B H W / 128) ceil(max(Cin, 4 Cout) / 128) exceeds the 2^31 - 1 workgroups of a grid";
+
+    template <typename T> static void repack(const void* w, void* wp, int Cin, int Cout, hipStream_t st) {
+        hipLaunchKernelGGL(convt_repack_kernel<T>, dim3(blocks((int64_t)Cin * Cout, 256)), dim3(256), 0, st, (const T*)w, (T*)wp, Cin, Cout);
     }
-    store4(dw + (long long)e * 4, v[0], v[1], v[2], v[3]);
-}
-
-// ---- host side -------------------------------------------------------------------------------------------------------------------
-constexpr int CONVT_MAX_SPLIT = 64;
-constexpr int CONVT_FILL = 512;            // workgroups wgrad aims for: a constant, not the device's CU count, so that the bits do not depend on the device
-constexpr int CONVT_MIN_KTILES = 8;        // K tiles (of 64 fp16 / 32 fp32 pixels) a split keeps at least
-constexpr int CONVT_DB_ROWS = 512;         // high-resolution pixels of a db slab at the least: 16 rows to each of a workgroup's 32 row threads
-constexpr int CONVT_DB_MAX = 256;          // slabs at the most
-constexpr long long CONVT_MAX_PIXELS = 1LL << 30;      // of the HIGH-resolution grid: 4 B H W
-
-inline long long tiles(long long n) { return (n + LT - 1) / LT; }
-inline int chunk_of(int dtype) { return dtype == MOGE_FP16 ? 8 : 4; }
-inline long long align16(long long n) { return (n + 15) / 16 * 16; }
-
-// wgrad's split of the low-resolution pixels: a function of (B H W, Cin, Cout, dtype) only.  `per` K tiles to a part, `parts` parts that have work (the
-// last one takes what is left); the workspace query and the launch both read this one result.
-struct ConvtSplit { int parts; long long per; };
-ConvtSplit convt_split(long long M, int Cin, int Cout, int dtype) {
-    const long long t = 4 * tiles(Cin) * tiles(Cout);
-    const long long ktiles = (M + LCPR * chunk_of(dtype) - 1) / (LCPR * chunk_of(dtype));
-    long long s = CONVT_FILL / t;
-    if (s > ktiles / CONVT_MIN_KTILES) s = ktiles / CONVT_MIN_KTILES;
-    if (s > CONVT_MAX_SPLIT) s = CONVT_MAX_SPLIT;
-    if (s < 1) s = 1;
-    const long long per = ktiles ? (ktiles + s - 1) / s : 1;
-    return ConvtSplit{ktiles ? (int)((ktiles + per - 1) / per) : 1, per};
-}
-// db's slabs: a function of the 4 B H W high-resolution pixels only
-int convt_db_split(long long M4) {
-    const long long s = (M4 + CONVT_DB_ROWS - 1) / CONVT_DB_ROWS;
-    return s < 1 ? 1 : (s > CONVT_DB_MAX ? CONVT_DB_MAX : (int)s);
-}
-
-struct ConvtWs { long long wp, part, dbpart, total; };          // byte offsets of the packed weight, the dw partials and the db partials
-ConvtWs convt_ws(long long M, int Cin, int Cout, int dtype) {
-    ConvtWs w;
-    const long long n = (long long)Cin * Cout;
-    w.wp = 0;
-    w.part = align16(4 * n * (dtype == MOGE_FP16 ? 2 : 4));
-    w.dbpart = w.part + 4LL * convt_split(M, Cin, Cout, dtype).parts * 4 * n;
-    w.total = w.dbpart + align16(4LL * convt_db_split(4 * M) * Cout);
-    return w;
-}
-
-int check_sizes(const char* fn, int dtype, int B, int H, int W, int Cin, int Cout) {
-    if (dtype != MOGE_FP32 && dtype != MOGE_FP16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: unknown dtype %d (MOGE_FP32 or MOGE_FP16)", fn, dtype);
-    const int ch = chunk_of(dtype);
-    if (B < 0) return moge_internal_fail(MOGE_ERR_INVALID, "%s: B < 0", fn);
-    if (H < 1) return moge_internal_fail(MOGE_ERR_INVALID, "%s: H = %d < 1", fn, H);
-    if (W < 1) return moge_internal_fail(MOGE_ERR_INVALID, "%s: W = %d < 1", fn, W);
-    if (Cin < 1 || Cin % ch) return moge_internal_fail(MOGE_ERR_INVALID, "%s: Cin = %d is not a positive multiple of %d elements (16-byte vector accesses)", fn, Cin, ch);
-    if (Cout < 1 || Cout % ch) return moge_internal_fail(MOGE_ERR_INVALID, "%s: Cout = %d is not a positive multiple of %d elements (16-byte vector accesses)", fn, Cout, ch);
-    if ((long long)B * H > CONVT_MAX_PIXELS / 4 || (long long)B * H * W > CONVT_MAX_PIXELS / 4)
-        return moge_internal_fail(MOGE_ERR_INVALID, "%s: 4 B H W exceeds 2^30 pixels of the (2H, 2W) grid", fn);
-    if ((long long)Cin * Cout > (1LL << 24)) return moge_internal_fail(MOGE_ERR_INVALID, "%s: Cin Cout exceeds 2^24", fn);
-    if (tiles((long long)B * H * W) * tiles(Cin > 4LL * Cout ? Cin : 4LL * Cout) > 0x7fffffffLL)
-        return moge_internal_fail(MOGE_ERR_INVALID, "%s: ceil(B H W / 128) ceil(max(Cin, 4 Cout) / 128) exceeds the 2^31 - 1 workgroups of a grid", fn);
-    return 0;
-}
-
-// an activation (B, H, W, C) read or written in place on a dense pixel grid: 16-byte aligned, pixel stride a multiple of 16 bytes and at least C
-int check_pixels(const char* fn, const char* name, const char* ldname, const void* p, int64_t ld, int C, int dtype) {
-    if (!p) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is null", fn, name);
-    if ((uintptr_t)p % 16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is not 16-byte aligned", fn, name);
-    if (ld < C || ld % chunk_of(dtype))
-        return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s = %lld is not a multiple of %d elements (16-byte vector accesses) of at least the channel count %d", fn, ldname,
-                                  (long long)ld, chunk_of(dtype), C);
-    return 0;
-}
-int check_vector(const char* fn, const char* name, const void* p, bool required) {
-    if (!p && required) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is null", fn, name);
-    if ((uintptr_t)p % 16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is not 16-byte aligned", fn, name);
-    return 0;
-}
-
-template <typename T>
-void launch_repack(const void* w, void* wp, int Cin, int Cout, hipStream_t st) {
-    hipLaunchKernelGGL(convt_repack_kernel<T>, dim3(blocks((int64_t)Cin * Cout, 256)), dim3(256), 0, st, (const T*)w, (T*)wp, Cin, Cout);
-}
-
-template <typename T>
-void launch_forward(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, char* ws, int M, int W, int Cin, int Cout, hipStream_t st) {
-    launch_repack<T>(w, ws, Cin, Cout, st);
-    hipLaunchKernelGGL(convt_kernel<T>, dim3((unsigned)(tiles(M) * tiles(4LL * Cout))), dim3(256), 0, st, (const T*)x, (long long)ldx, (const T*)ws, (const T*)bias, (T*)y,
-                       (long long)ldy, M, W, Cin, Cout, (int)tiles(4LL * Cout));
-}
-
-template <typename T>
-void launch_backward(const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, char* ws, const ConvtWs& o, int M, int W,
-                     int Cin, int Cout, int dtype, hipStream_t st) {
-    if (dx) {
-        launch_repack<T>(w, ws + o.wp, Cin, Cout, st);
-        hipLaunchKernelGGL(convt_dgrad_kernel<T>, dim3((unsigned)(tiles(M) * tiles(Cin))), dim3(256), 0, st, (const T*)dy, (long long)lddy, (const T*)(ws + o.wp), (T*)dx,
+    template <typename T>
+    static void forward(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, void* wp, int M, int, int W, int Cin, int Cout, hipStream_t st) {
+        repack<T>(w, wp, Cin, Cout, st);
+        hipLaunchKernelGGL(convt_kernel<T>, dim3((unsigned)(tiles(M) * tiles(4LL * Cout))), dim3(256), 0, st, (const T*)x, (long long)ldx, (const T*)wp, (const T*)bias, (T*)y,
+                           (long long)ldy, M, W, Cin, Cout, (int)tiles(4LL * Cout));
+    }
+    template <typename T>
+    static void dgrad(const void* dy, int64_t lddy, const void* w, void* wp, void* dx, int64_t lddx, int M, int, int W, int Cin, int Cout, hipStream_t st) {
+        repack<T>(w, wp, Cin, Cout, st);
+        hipLaunchKernelGGL(convt_dgrad_kernel<T>, dim3((unsigned)(tiles(M) * tiles(Cin))), dim3(256), 0, st, (const T*)dy, (long long)lddy, (const T*)wp, (T*)dx,
                            (long long)lddx, M, W, Cout, Cin, (int)tiles(Cin));
     }
-    if (dw) {
-        constexpr int BK = LCPR * TT<T>::CH;
-        const ConvtSplit sp = convt_split(M, Cin, Cout, dtype);
-        const int split = sp.parts, kper = (int)sp.per * BK;          // pixels of a part
-        float* part = (float*)(ws + o.part);
+    template <typename T>
+    static void wgrad(const void* x, int64_t ldx, const void* dy, int64_t lddy, float* part, int M, int, int W, int Cin, int Cout, int split, int kper, hipStream_t st) {
         hipLaunchKernelGGL(convt_wgrad_kernel<T>, dim3((unsigned)(tiles(Cin) * tiles(Cout)), 4, (unsigned)split), dim3(256), 0, st, (const T*)x, (long long)ldx, (const T*)dy,
                            (long long)lddy, part, M, W, Cin, Cout, kper, (int)tiles(Cout));
-        hipLaunchKernelGGL(convt_reduce_kernel<T>, dim3(blocks((int64_t)Cin * Cout, 256)), dim3(256), 0, st, (const float*)part, (T*)dw, Cin * Cout, split);
     }
-    if (db) {
-        const int M4 = 4 * M, S = convt_db_split(M4);
-        const int rows = (M4 + S - 1) / S;
-        float* part = (float*)(ws + o.dbpart);
-        hipLaunchKernelGGL(conv_colsum_kernel<T>, dim3(blocks(Cout, 8 * TT<T>::CH), (unsigned)S), dim3(256), 0, st, (const T*)dy, (long long)lddy, part, M4, Cout, rows);
-        hipLaunchKernelGGL(conv_colsum_reduce_kernel<T>, dim3(blocks(Cout, 256)), dim3(256), 0, st, (const float*)part, (T*)db, Cout, S);
-    }
-}
+};
 
 }  // namespace
 
 extern "C" {
 
 int moge_convt2x2_workspace(int B, int H, int W, int Cin, int Cout, int dtype, int64_t* forward_bytes, int64_t* backward_bytes) {
-    static const char* fn = "moge_convt2x2_workspace";
-    if (!forward_bytes) return moge_internal_fail(MOGE_ERR_INVALID, "%s: forward_bytes is null", fn);
-    if (!backward_bytes) return moge_internal_fail(MOGE_ERR_INVALID, "%s: backward_bytes is null", fn);
-    *forward_bytes = *backward_bytes = 0;
-    if (int e = check_sizes(fn, dtype, B, H, W, Cin, Cout)) return e;
-    const ConvtWs o = convt_ws((long long)B * H * W, Cin, Cout, dtype);
-    *forward_bytes = o.part;
-    *backward_bytes = o.total;
-    return 0;
+    return conv_workspace<ConvT2x2>(B, H, W, Cin, Cout, dtype, forward_bytes, backward_bytes);
 }
 
 int moge_convt2x2_forward(int dtype, const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, int B, int H, int W, int Cin, int Cout, void* workspace,
                           void* stream) {
-    static const char* fn = "moge_convt2x2_forward";
-    if (int e = check_sizes(fn, dtype, B, H, W, Cin, Cout)) return e;
-    if (B == 0) return 0;
-    if (int e = check_pixels(fn, "x", "ldx", x, ldx, Cin, dtype)) return e;
-    if (int e = check_vector(fn, "w", w, true)) return e;
-    if (int e = check_vector(fn, "bias", bias, false)) return e;
-    if (int e = check_pixels(fn, "y", "ldy", y, ldy, Cout, dtype)) return e;
-    if (int e = check_vector(fn, "workspace", workspace, true)) return e;
-    if (dtype == MOGE_FP16) launch_forward<f16>(x, ldx, w, bias, y, ldy, (char*)workspace, B * H * W, W, Cin, Cout, (hipStream_t)stream);
-    else launch_forward<float>(x, ldx, w, bias, y, ldy, (char*)workspace, B * H * W, W, Cin, Cout, (hipStream_t)stream);
-    return launched("moge_convt2x2_forward: launch failed");
+    return conv_forward<ConvT2x2>(dtype, x, ldx, w, bias, y, ldy, B, H, W, Cin, Cout, workspace, stream);
 }
 
 int moge_convt2x2_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, void* workspace, int B,
                            int H, int W, int Cin, int Cout, void* stream) {
-    static const char* fn = "moge_convt2x2_backward";
-    if (int e = check_sizes(fn, dtype, B, H, W, Cin, Cout)) return e;
-    if (B == 0 || (!dx && !dw && !db)) return 0;
-    if (int e = check_pixels(fn, "dy", "lddy", dy, lddy, Cout, dtype)) return e;
-    if (dx) {
-        if (int e = check_vector(fn, "w", w, true)) return e;
-        if (int e = check_pixels(fn, "dx", "lddx", dx, lddx, Cin, dtype)) return e;
-    }
-    if (dw) {
-        if (int e = check_pixels(fn, "x", "ldx", x, ldx, Cin, dtype)) return e;
-        if (int e = check_vector(fn, "dw", dw, true)) return e;
-    }
-    if (int e = check_vector(fn, "db", db, false)) return e;
-    if (int e = check_vector(fn, "workspace", workspace, true)) return e;
-    const int M = B * H * W;
-    const ConvtWs o = convt_ws(M, Cin, Cout, dtype);
-    if (dtype == MOGE_FP16) launch_backward<f16>(x, ldx, w, dy, lddy, dx, lddx, dw, db, (char*)workspace, o, M, W, Cin, Cout, dtype, (hipStream_t)stream);
-    else launch_backward<float>(x, ldx, w, dy, lddy, dx, lddx, dw, db, (char*)workspace, o, M, W, Cin, Cout, dtype, (hipStream_t)stream);
-    return launched("moge_convt2x2_backward: launch failed");
+    return conv_backward<ConvT2x2>(dtype, x, ldx, w, dy, lddy, dx, lddx, dw, db, workspace, B, H, W, Cin, Cout, stream);
 }
 
 }  // extern "C"

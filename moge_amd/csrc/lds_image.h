@@ -1,8 +1,10 @@
 // Swizzled LDS images of 16-byte chunks, shared by the trainable kernels (attention_grad.hip, linear_grad.hip, conv_grad.hip, convt_grad.hip): a tile is kept as
 // [row][chunks along the contraction index] with the XOR chunk swizzle of common.h, and an operand whose contraction index is strided in memory is
 // transposed on its way in, element by element, into the same form.  One code path for both storage types.  Below them, the 128-row operand tiles of
-// the product family of linear_grad.hip, conv_grad.hip and convt_grad.hip: their loads into registers and their staging into an image, and what the two
-// gathered files share beyond that: the MFMA loop over a staged K tile, the accumulator tile's store and the slab column sum.
+// the product family of linear_grad.hip, conv_grad.hip and convt_grad.hip: their loads into registers and their staging into an image (lin_load, lin_stage),
+// the workgroup's thread and tile coordinates (LinTile), the MFMA loop over a staged K tile and the accumulator tile's zeroing and store (lin_mma, lin_zero,
+// lin_store), and the family's small kernels: the slab column sum with its slab reduce and the tap reduce of a split weight gradient.  The host half of the
+// family is grad_host.h.
 #pragma once
 #include "common.h"
 
@@ -76,10 +78,19 @@ __device__ __forceinline__ void lin_stage(char* img, const u32x4 (&r)[4], int ti
     }
 }
 
-// ---- the MFMA loop, the accumulator tile and its store, and the slab column sum of the gathered kernels (conv_grad.hip, convt_grad.hip) ----
-// the 2 x 2 mma_step tiles of a wave over one staged K tile (linear_kernel's loop)
+// ---- the workgroup's place, the MFMA loop, the accumulator tile and its store, the column sum and the tap reduce of the family's kernels ----
+// a thread's place in the 256-thread workgroup and the workgroup's 128 x 128 tile of C: blockIdx.x = ti tiles_j + tj, the four waves 2 x 2 tiles of 64 x 64
+// (the kernels copy these into locals and hand the helpers below plain ints: with the struct itself passed on, hipcc allocates registers differently)
+struct LinTile { int tid, hi, l31, i0, j0, wi, wj; };
+__device__ __forceinline__ LinTile lin_tile(int tiles_j) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
+    return LinTile{tid, lane >> 5, lane & 31, ti * LT, tj * LT, (wave >> 1) * 64, (wave & 1) * 64};
+}
+
+// the 2 x 2 mma_step tiles of a wave over one staged K tile
 template <typename T>
-__device__ __forceinline__ void conv_mma(f32x16 (&acc)[2][2], const char* sA, const char* sB, int wi, int wj, int l31, int hi) {
+__device__ __forceinline__ void lin_mma(f32x16 (&acc)[2][2], const char* sA, const char* sB, int wi, int wj, int l31, int hi) {
 #pragma unroll
     for (int s = 0; s < LCPR / 2; s++) {
         u32x4 fa[2], fb[2];
@@ -90,11 +101,11 @@ __device__ __forceinline__ void conv_mma(f32x16 (&acc)[2][2], const char* sA, co
 #pragma unroll
         for (int a = 0; a < 2; a++)
 #pragma unroll
-            for (int b = 0; b < 2; b++) mma_step<T>(acc[a][b], fb[b], fa[a]);
+            for (int b = 0; b < 2; b++) mma_step<T>(acc[a][b], fb[b], fa[a]);      // B is the primitive's first operand: the row of C on the lane, its columns in the registers
     }
 }
 
-__device__ __forceinline__ void conv_zero(f32x16 (&acc)[2][2]) {
+__device__ __forceinline__ void lin_zero(f32x16 (&acc)[2][2]) {
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
@@ -103,10 +114,10 @@ __device__ __forceinline__ void conv_zero(f32x16 (&acc)[2][2]) {
             for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
 }
 
-// the row of C on the lane, its columns in the registers: four consecutive columns per store (linear_kernel's epilogue)
+// the tile's part of C (I, J), plus bias[j] where there is one: the row of C on the lane, four consecutive columns per store
 template <typename TO, typename TB>
-__device__ __forceinline__ void conv_store(const f32x16 (&acc)[2][2], TO* __restrict__ C, long long ldc, const TB* __restrict__ bias, int i0, int I, int j0, int J, int wi, int wj,
-                                           int l31, int hi) {
+__device__ __forceinline__ void lin_store(const f32x16 (&acc)[2][2], TO* __restrict__ C, long long ldc, const TB* __restrict__ bias, int i0, int I, int j0, int J, int wi, int wj,
+                                          int l31, int hi) {
 #pragma unroll
     for (int a = 0; a < 2; a++) {
         const int i = i0 + wi + a * 32 + l31;
@@ -125,10 +136,11 @@ __device__ __forceinline__ void conv_store(const f32x16 (&acc)[2][2], TO* __rest
     }
 }
 
-// part[z][o] = sum of dy[m][o] over the slab of rows [z rows, min(M, (z + 1) rows)): a workgroup takes 8 column chunks, 32 threads per chunk sum the
-// rows r, r + 32, ... of the slab in that order, then the 32 partials are added in the order r = 0 ... 31 (lin_colsum_kernel's order, per slab)
-template <typename T>
-__global__ __launch_bounds__(256) void conv_colsum_kernel(const T* __restrict__ dy, long long lddy, float* __restrict__ part, int M, int N, int rows) {
+// out[z][o] = sum of dy[m][o] over the slab of rows [z rows, min(M, (z + 1) rows)), z = blockIdx.y: a workgroup takes 8 column chunks, 32 threads per chunk
+// sum the rows r, r + 32, ... of the slab in that order, then the 32 partials are added in the order r = 0 ... 31.  TO = T with one slab of M rows is db
+// itself (linear_grad.hip); TO = float gives the partials of lin_colsum_reduce_kernel.
+template <typename T, typename TO>
+__global__ __launch_bounds__(256) void lin_colsum_kernel(const T* __restrict__ dy, long long lddy, TO* __restrict__ out, int M, int N, int rows) {
     constexpr int CH = TT<T>::CH;
     __shared__ float sum[32][8 * CH + 1];
     const int tid = threadIdx.x, c = tid & 7, r = tid >> 3;
@@ -152,19 +164,34 @@ __global__ __launch_bounds__(256) void conv_colsum_kernel(const T* __restrict__ 
         if (col < N) {
             float v = sum[0][tid];
             for (int i = 1; i < 32; i++) v += sum[i][tid];
-            part[(long long)blockIdx.y * N + col] = v;
+            out[(long long)blockIdx.y * N + col] = (TO)v;
         }
     }
 }
 
 // db[o] = the slab sums added in slab order, rounded once
 template <typename T>
-__global__ __launch_bounds__(256) void conv_colsum_reduce_kernel(const float* __restrict__ part, T* __restrict__ db, int N, int S) {
+__global__ __launch_bounds__(256) void lin_colsum_reduce_kernel(const float* __restrict__ part, T* __restrict__ db, int N, int S) {
     const int o = blockIdx.x * 256 + threadIdx.x;
     if (o >= N) return;
     float v = part[o];
     for (int z = 1; z < S; z++) v += part[(long long)z * N + o];
     db[o] = (T)v;
+}
+
+// dw[e][tap] = the S partials part[z][tap][e] added in split order, rounded once; one thread per channel pair e, four taps stored as one vector
+template <typename T, int TAPS>
+__global__ __launch_bounds__(256) void lin_tap_reduce_kernel(const float* __restrict__ part, T* __restrict__ dw, int n, int S) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    float v[TAPS];
+#pragma unroll
+    for (int tap = 0; tap < TAPS; tap++) {
+        v[tap] = part[(long long)tap * n + e];
+        for (int z = 1; z < S; z++) v[tap] += part[((long long)z * TAPS + tap) * n + e];
+        if constexpr (TAPS != 4) dw[(long long)e * TAPS + tap] = (T)v[tap];
+    }
+    if constexpr (TAPS == 4) store4(dw + (long long)e * 4, v[0], v[1], v[2], v[3]);
 }
 
 }  // namespace

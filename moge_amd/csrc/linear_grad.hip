@@ -14,13 +14,13 @@
 // Tails: a row past the tensor is clamped on load where it is a row of C (its results are not stored) and is ZERO where it is the contraction index
 // (wgrad: M), as is every chunk past the contraction range; nothing outside [0, rows) x [0, cols) is addressed; stores are guarded.
 // No atomics.  wgrad may split M over grid.z (lin_split: a function of the sizes only); the fp32 partials go to the workspace and lin_reduce_kernel
-// adds them in split order.  db is one column-sum launch in a fixed order.
-#include "common.h"
-#include "lds_image.h"
+// adds them in split order.  db is one column-sum launch in a fixed order (lin_colsum_kernel<T, T> of lds_image.h, one slab).  The tile arithmetic,
+// the leading-dimension check and the split's target are grad_host.h's, shared with conv_grad.hip and convt_grad.hip.
+#include "grad_host.h"
 
 namespace {
 
-// C (I, J) = A B^T over the contraction range [z kper, min(Kc, (z + 1) kper)), z = blockIdx.z; C += z * zstride (the split's fp32 partials)
+// C (I, J) = A B^T over the contraction range [z kper, min(Kc, (z + 1) kper)), z = blockIdx.z, stored at C + z zstride (the split's fp32 partials)
 template <typename T, typename TO, bool TA, bool TB>
 __global__ __launch_bounds__(256) void linear_kernel(const T* __restrict__ A, long long lda, const T* __restrict__ B, long long ldb, const T* __restrict__ bias,
                                                      TO* __restrict__ C, long long ldc, int I, int J, int Kc, int kper, long long zstride, int tiles_j) {
@@ -29,21 +29,13 @@ __global__ __launch_bounds__(256) void linear_kernel(const T* __restrict__ A, lo
     __shared__ __attribute__((aligned(16))) char sA[LT * LCPR * 16];      // [i][k]
     __shared__ __attribute__((aligned(16))) char sB[LT * LCPR * 16];      // [j][k]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hi = lane >> 5, l31 = lane & 31;
-    const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
-    const int i0 = ti * LT, j0 = tj * LT;
-    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+    const LinTile wg = lin_tile(tiles_j);
+    const int tid = wg.tid, hi = wg.hi, l31 = wg.l31, i0 = wg.i0, j0 = wg.j0, wi = wg.wi, wj = wg.wj;
     const int kbeg = blockIdx.z * kper;
     const int kend = Kc - kbeg < kper ? Kc : kbeg + kper;
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
+    lin_zero(acc);
 
     u32x4 ra[4], rb[4];
     lin_load<T, TA>(ra, A, lda, i0, I, kbeg, kend, tid);
@@ -57,37 +49,9 @@ __global__ __launch_bounds__(256) void linear_kernel(const T* __restrict__ A, lo
             lin_load<T, TA>(ra, A, lda, i0, I, k0 + BK, kend, tid);
             lin_load<T, TB>(rb, B, ldb, j0, J, k0 + BK, kend, tid);
         }
-        // the row of C on the lane, its columns in the registers (B is the primitive's first operand): four consecutive columns per store
-#pragma unroll
-        for (int s = 0; s < LCPR / 2; s++) {
-            u32x4 fa[2], fb[2];
-#pragma unroll
-            for (int a = 0; a < 2; a++) fa[a] = lds_chunk<LCPR>(sA, wi + a * 32 + l31, (2 * s + hi) ^ lin_x(wi + a * 32 + l31));
-#pragma unroll
-            for (int b = 0; b < 2; b++) fb[b] = lds_chunk<LCPR>(sB, wj + b * 32 + l31, (2 * s + hi) ^ lin_x(wj + b * 32 + l31));
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++) mma_step<T>(acc[a][b], fb[b], fa[a]);
-        }
+        lin_mma<T>(acc, sA, sB, wi, wj, l31, hi);
     }
-    C += blockIdx.z * zstride;
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-        const int i = i0 + wi + a * 32 + l31;
-        if (i >= I) continue;
-        TO* crow = C + i * ldc;
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; g4++) {
-                const int j = j0 + wj + b * 32 + 8 * g4 + 4 * hi;
-                if (j >= J) continue;                                   // J is a multiple of 4: a group of four is inside or outside
-                float bv[4] = {0.f, 0.f, 0.f, 0.f};
-                if (bias) load4(bias + j, bv);
-                store4(crow + j, acc[a][b][4 * g4] + bv[0], acc[a][b][4 * g4 + 1] + bv[1], acc[a][b][4 * g4 + 2] + bv[2], acc[a][b][4 * g4 + 3] + bv[3]);
-            }
-    }
+    lin_store<TO, T>(acc, C + blockIdx.z * zstride, ldc, bias, i0, I, j0, J, wi, wj, l31, hi);
 }
 
 // dW (N, K) = the S fp32 partials of the split added in split order, rounded once; four elements per thread
@@ -109,74 +73,28 @@ __global__ __launch_bounds__(256) void lin_reduce_kernel(const float* __restrict
     store4(dw + n * lddw + k, s[0], s[1], s[2], s[3]);
 }
 
-// db[n] = sum_m dY[m][n]: a workgroup takes 8 column chunks, 32 threads per chunk sum the rows m = r, r + 32, ... in that order, then the 32 partials
-// are added in the order r = 0 ... 31
-template <typename T>
-__global__ __launch_bounds__(256) void lin_colsum_kernel(const T* __restrict__ dy, long long lddy, T* __restrict__ db, int M, int N) {
-    constexpr int CH = TT<T>::CH;
-    __shared__ float part[32][8 * CH + 1];
-    const int tid = threadIdx.x, c = tid & 7, r = tid >> 3;
-    const int n = (blockIdx.x * 8 + c) * CH;
-    float s[CH];
-#pragma unroll
-    for (int e = 0; e < CH; e++) s[e] = 0.f;
-    if (n < N)
-        for (int m = r; m < M; m += 32) {
-            const typename Vec<T>::type v = __builtin_bit_cast(typename Vec<T>::type, ldg16(dy + m * lddy + n));
-#pragma unroll
-            for (int e = 0; e < CH; e++) s[e] += (float)v[e];
-        }
-#pragma unroll
-    for (int e = 0; e < CH; e++) part[r][c * CH + e] = s[e];
-    __syncthreads();
-    if (tid < 8 * CH) {
-        const int col = blockIdx.x * 8 * CH + tid;
-        if (col < N) {
-            float t = part[0][tid];
-            for (int i = 1; i < 32; i++) t += part[i][tid];
-            db[col] = (T)t;
-        }
-    }
-}
-
 // ---- host side -------------------------------------------------------------------------------------------------------------------
 constexpr int LIN_MAX_SPLIT = 32;
 constexpr int LIN_FILL = 256;              // workgroups wgrad aims for: a constant, not the device's CU count, so that the bits do not depend on the device
 constexpr int LIN_MIN_KTILES = 8;          // K tiles a split keeps at least
 
-inline long long tiles(int n) { return ((long long)n + LT - 1) / LT; }
-inline int chunk_of(int dtype) { return dtype == MOGE_FP16 ? 8 : 4; }
-
-// wgrad's split of M: a function of (M, N, K, dtype) only.  1 = no split, no workspace.
-int lin_split(int M, int N, int K, int dtype) {
-    const long long t = tiles(N) * tiles(K);
-    const long long ktiles = ((long long)M + LCPR * chunk_of(dtype) - 1) / (LCPR * chunk_of(dtype));
-    long long s = LIN_FILL / t;
-    if (s > ktiles / LIN_MIN_KTILES) s = ktiles / LIN_MIN_KTILES;
-    if (s > LIN_MAX_SPLIT) s = LIN_MAX_SPLIT;
-    return s < 1 ? 1 : (int)s;
-}
+// wgrad's split of M: a function of (M, N, K, dtype) only.  1 = no split, no workspace.  Every part is launched, one without work included.
+int lin_split(int M, int N, int K, int dtype) { return (int)split_target(M, tiles(N) * tiles(K), LIN_FILL, LIN_MAX_SPLIT, LIN_MIN_KTILES, dtype); }
 
 int check_sizes(const char* fn, int dtype, int M, int N, int K) {
-    if (dtype != MOGE_FP32 && dtype != MOGE_FP16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: unknown dtype %d (MOGE_FP32 or MOGE_FP16)", fn, dtype);
-    const int ch = chunk_of(dtype);
+    if (int e = check_dtype(fn, dtype)) return e;
     if (M < 0) return moge_internal_fail(MOGE_ERR_INVALID, "%s: M < 0", fn);
-    if (N < 1 || N % ch) return moge_internal_fail(MOGE_ERR_INVALID, "%s: N = %d is not a positive multiple of %d elements (16-byte vector accesses)", fn, N, ch);
-    if (K < 1 || K % ch) return moge_internal_fail(MOGE_ERR_INVALID, "%s: K = %d is not a positive multiple of %d elements (16-byte vector accesses)", fn, K, ch);
+    if (int e = check_count(fn, "N", N, dtype)) return e;
+    if (int e = check_count(fn, "K", K, dtype)) return e;
     if (tiles(M) * tiles(N) > 0x7fffffffLL || tiles(M) * tiles(K) > 0x7fffffffLL || tiles(N) * tiles(K) > 0x7fffffffLL)
         return moge_internal_fail(MOGE_ERR_INVALID, "%s: ceil(M / 128) ceil(N / 128), ceil(M / 128) ceil(K / 128) or ceil(N / 128) ceil(K / 128) exceeds the 2^31 - 1 workgroups of a grid",
                                   fn);
     return 0;
 }
 
-// a (rows, cols) matrix read or written in place: 16-byte aligned, leading dimension a multiple of 16 bytes and at least the row length
-int check_matrix(const char* fn, const char* name, const char* ldname, const void* p, int64_t ld, int cols, int dtype) {
-    if (!p) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is null", fn, name);
-    if ((uintptr_t)p % 16) return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s is not 16-byte aligned", fn, name);
-    if (ld < cols || ld % chunk_of(dtype))
-        return moge_internal_fail(MOGE_ERR_INVALID, "%s: %s = %lld is not a multiple of %d elements (16-byte vector accesses) of at least the row length %d", fn, ldname,
-                                  (long long)ld, chunk_of(dtype), cols);
-    return 0;
+// a (rows, cols) matrix read or written in place
+inline int check_matrix(const char* fn, const char* name, const char* ldname, const void* p, int64_t ld, int cols, int dtype) {
+    return check_rows(fn, name, ldname, p, ld, cols, dtype, "row length");
 }
 
 template <typename T, typename TO, bool TA, bool TB>
@@ -198,7 +116,7 @@ void launch_backward(const void* x, int64_t ldx, const void* w, int64_t ldw, con
         const long long quads = (long long)N * K / 4;
         hipLaunchKernelGGL(lin_reduce_kernel<T>, dim3(blocks(quads, 256)), dim3(256), 0, st, (const float*)ws, (T*)dw, (long long)lddw, K, quads, split);
     }
-    if (db) hipLaunchKernelGGL(lin_colsum_kernel<T>, dim3(blocks(N, 8 * TT<T>::CH)), dim3(256), 0, st, (const T*)dy, (long long)lddy, (T*)db, M, N);
+    if (db) launch_colsum<T, T>(dy, lddy, (T*)db, M, N, 1, st);          // one slab: db itself, in one launch
 }
 
 }  // namespace

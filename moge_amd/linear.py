@@ -51,10 +51,15 @@ def _rows(t: torch.Tensor) -> torch.Tensor:
     return _in_place(t.reshape(-1, t.shape[-1]))
 
 
-def _check(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> None:
-    for name, t in (("input", x), ("weight", w), ("bias", bias)):
+def _built_dtypes(module: str, input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> None:
+    """Refuses, for `moge_amd.<module>` and by argument name, a dtype the kernels are not built for."""
+    for name, t in (("input", input), ("weight", weight), ("bias", bias)):
         if t is not None and t.dtype not in _DTYPE:
-            raise NotImplementedError(f"moge_amd.linear: {name} is {t.dtype}; only float16 and float32 are built")
+            raise NotImplementedError(f"moge_amd.{module}: {name} is {t.dtype}; only float16 and float32 are built")
+
+
+def _check(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> None:
+    """The shapes and the common dtype (after _built_dtypes)."""
     if w.dim() != 2 or x.dim() < 1 or x.shape[-1] != w.shape[1] or (bias is not None and bias.shape != (w.shape[0],)):
         raise ValueError(f"moge_amd.linear: input (..., K), weight (N, K) and bias (N,) expected, got {tuple(x.shape)}, {tuple(w.shape)}"
                          f"{'' if bias is None else ', ' + str(tuple(bias.shape))}")
@@ -70,6 +75,7 @@ def _check(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> No
 def forward(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x (M, K), w (N, K), bias (N,) or None -> y (M, N) = x w^T + bias.  `out`: an (M, N) view to write through its row stride.  Not recorded
     by autograd."""
+    _built_dtypes("linear", x, w, bias)
     _check(x, w, bias)
     dev = L.device_of("linear", x, w, bias, out)
     (M, K), N = x.shape, w.shape[0]
@@ -126,40 +132,45 @@ class _Linear(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad):
         x, w = ctx.saved_tensors
-        need_x, need_w, need_b = ctx.needs_input_grad
         dy = _rows(grad)
         M, N, K = dy.shape[0], ctx.n_out, ctx.in_shape[-1]
-        dx = torch.empty((M, K), dtype=dy.dtype, device=dy.device) if need_x else None
-        dw = torch.empty((N, K), dtype=dy.dtype, device=dy.device) if need_w else None
-        db = torch.empty((N,), dtype=dy.dtype, device=dy.device) if need_b else None
-        if M == 0:
-            for t in (dw, db):
-                if t is not None:
-                    t.zero_()
-        elif need_x or need_w or need_b:
-            backward(x, w, dy, dx, dw, db)
+        dx, dw, db = _gradients(ctx, backward, x, w, dy, (M, K), (N, K), M == 0)
         return None if dx is None else dx.view(ctx.in_shape), dw, db
 
 
-def _autocast(*tensors: Optional[torch.Tensor]):
-    """What F.linear does under torch.autocast: float tensors go to the autocast dtype, through autograd, so that an fp32 parameter receives an
-    fp32 gradient.  float16 only."""
+def _autocast(module: str, *tensors: Optional[torch.Tensor]):
+    """What F.linear does under torch.autocast, for `moge_amd.<module>`: float tensors go to the autocast dtype, through autograd, so that an fp32
+    parameter receives an fp32 gradient.  float16 only."""
     new_api = hasattr(torch, "get_autocast_dtype")
     if not (torch.is_autocast_enabled("cuda") if new_api else torch.is_autocast_enabled()):
         return tensors
     dtype = torch.get_autocast_dtype("cuda") if new_api else torch.get_autocast_gpu_dtype()
     if dtype != torch.float16:
-        raise NotImplementedError(f"moge_amd.linear: autocast dtype {dtype}; only float16 is built")
+        raise NotImplementedError(f"moge_amd.{module}: autocast dtype {dtype}; only float16 is built")
     return tuple(t.to(dtype) if t is not None and t.is_floating_point() else t for t in tensors)
+
+
+def _gradients(ctx, run, x, w, dy: torch.Tensor, dx_shape, dw_shape, empty: bool):
+    """(dx, dw, db) of an autograd backward in dy's dtype: each allocated where ctx needs it (db has dy's last dimension), else None; dw and db are zero where the op is `empty`
+    (no rows), otherwise run(x, w, dy, dx, dw, db) fills what is there."""
+    need_x, need_w, need_b = ctx.needs_input_grad
+    dx = torch.empty(dx_shape, dtype=dy.dtype, device=dy.device) if need_x else None
+    dw = torch.empty(dw_shape, dtype=dy.dtype, device=dy.device) if need_w else None
+    db = torch.empty((dy.shape[-1],), dtype=dy.dtype, device=dy.device) if need_b else None
+    if empty:
+        for t in (dw, db):
+            if t is not None:
+                t.zero_()
+    elif need_x or need_w or need_b:
+        run(x, w, dy, dx, dw, db)
+    return dx, dw, db
 
 
 def linear(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """F.linear for fp16 / fp32 GPU tensors, differentiable: input (..., K), weight (N, K), bias (N,) -> (..., N) in the input's dtype (the
     autocast dtype under torch.autocast)."""
-    for name, t in (("input", input), ("weight", weight), ("bias", bias)):
-        if t is not None and t.dtype not in _DTYPE:
-            raise NotImplementedError(f"moge_amd.linear: {name} is {t.dtype}; only float16 and float32 are built")
-    input, weight, bias = _autocast(input, weight, bias)
+    _built_dtypes("linear", input, weight, bias)
+    input, weight, bias = _autocast("linear", input, weight, bias)
     _check(input, weight, bias)
     L.device_of("linear", input, weight, bias)
     return _Linear.apply(input, weight, bias)

@@ -29,7 +29,7 @@ def test_symbols_are_declared_exported_and_bound():
     assert sorted(n for n in L.EXPORTS if n.startswith("moge_convt2x2_")) == NAMES
     assert not any(n.startswith("moge_conv1x1") for n in L.EXPORTS)         # the 1x1 conv is moge_linear_*
     assert L.lib.moge_abi_version() == 5                                   # purely additive
-    assert "convt_grad.hip" in B.SOURCES and "lds_image.h" in B.HEADERS
+    assert "convt_grad.hip" in B.SOURCES and "lds_image.h" in B.HEADERS and "grad_host.h" in B.HEADERS
     assert L.SIGNATURES["moge_convt2x2_forward"] == L.SIGNATURES["moge_conv3x3_forward"]          # the conventions of moge_conv3x3_*, word for word
     assert L.SIGNATURES["moge_convt2x2_backward"] == L.SIGNATURES["moge_conv3x3_backward"]
     assert L.SIGNATURES["moge_convt2x2_workspace"] == L.SIGNATURES["moge_conv3x3_workspace"]

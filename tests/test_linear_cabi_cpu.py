@@ -26,7 +26,7 @@ def test_symbols_are_declared_exported_and_bound():
         assert name in L.EXPORTS and getattr(L.lib, name).argtypes is not None, name
     assert sorted(n for n in L.EXPORTS if n.startswith("moge_linear_")) == NAMES
     assert L.lib.moge_abi_version() == 5                                   # purely additive
-    assert "linear_grad.hip" in B.SOURCES and "lds_image.h" in B.HEADERS
+    assert "linear_grad.hip" in B.SOURCES and "lds_image.h" in B.HEADERS and "grad_host.h" in B.HEADERS
     assert (L.FP32, L.FP16) == (FP32, FP16)
 
 
