@@ -76,6 +76,14 @@ __device__ __forceinline__ void align_fetch_signed(const AlignRow& r, int j, flo
     x *= s; y *= s;
 }
 
+// a x - y as the reference forms it (:47, :82): two torch ops, the product rounded to float before the subtraction.  Written as a * x - y, or with
+// __fmul_rn / __fsub_rn (plain operators in hipcc's headers), the compiler fuses the two into one fma (-ffp-contract=fast-honor-pragmas is hipcc's
+// default), which keeps the product's low bits: where a row is fit exactly the loss is then rounding noise of another size than the reference's.
+__device__ __forceinline__ float align_residual(float a, float x, float y) {
+#pragma clang fp contract(off)
+    return a * x - y;
+}
+
 __device__ __forceinline__ double warp_incl_scan(double v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -176,7 +184,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_l1_kernel(const AlignArgs
     for (int j = tid; j < NE; j += ALIGN_THREADS) {
         float x, y, w;
         align_fetch_signed(r, j, x, y, w);
-        part += (double)(w * fabsf(a * x - y));                                        // :82
+        part += (double)(w * fabsf(align_residual(a, x, y)));                          // :82
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
@@ -313,7 +321,7 @@ __device__ __forceinline__ void trunc_event(int e, int NE, const float* wxa, con
 
 // one residual term as the reference forms it (_compute_residual, :47): |a x - y| * w clamped to trunc, each step rounded to float
 __device__ __forceinline__ float trunc_term(float a, float x, float y, float w, float trunc) {
-    return fminf(__fmul_rn(fabsf(__fsub_rn(__fmul_rn(a, x), y)), w), trunc);
+    return fminf(fabsf(align_residual(a, x, y)) * w, trunc);
 }
 
 // (f, j) beats (bf, bj): smaller objective, on a tie the later element (scatter_min's last write); j < 0 = nothing
