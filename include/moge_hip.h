@@ -895,6 +895,51 @@ int moge_convt2x2_forward(int dtype, const void* x, int64_t ldx, const void* w, 
 int moge_convt2x2_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, void* workspace, int B,
                            int H, int W, int Cin, int Cout, void* stream);
 
+/* ---- trainable bilinear resize: F.interpolate / nn.Upsample with mode bilinear, align_corners False, no antialias, and its input gradient (python
+ * mirror moge_amd/resample.py, csrc/resample_grad.hip) ---------------------------------------------------------------------
+ * One axis with n_in input and n_out output samples and scale sigma (n_in / n_out where a size was given, 1 / scale_factor otherwise):
+ *   s(o) = max(sigma (o + 0.5) - 0.5, 0)    i0 = min(floor s, n_in - 1)    i1 = min(i0 + 1, n_in - 1)    l1 = s - i0    l0 = 1 - l1
+ *   y [b,o,p,c] = sum_{a,a' in {0,1}} la^H(o) la'^W(p) x[b, ia^H(o), ia'^W(p), c]            dx = the transpose of that map applied to dy
+ * The conventions are those of moge_conv3x3_*: stateless, queued on `stream`, nothing waits; dtype MOGE_FP32 or MOGE_FP16 is the storage type, every
+ * sum is fp32 and a result is rounded once.  x and dx are NHWC (B, Hin, Win, C), y and dy (B, Hout, Wout, C), each on a dense pixel grid and read or
+ * written in place through its pixel stride ld* (elements, at least C), the pointer aligned to its element.  Where C is a multiple of 16 bytes and
+ * both tensors of a call have 16-byte aligned pointers and pixel strides, channels move in 16-byte accesses; otherwise element by element, with the
+ * same bits.  Nothing outside [0, pixels) x [0, C) of any tensor is addressed.  C, Hin, Win, Hout, Wout >= 1; B >= 0 (B = 0 is no work and no error,
+ * whatever the pointers); scale_h, scale_w positive and finite.
+ * workspace: forward_bytes = 0 (the forward's workspace is not read and may be NULL); backward_bytes = 4 (Hin + 1) rounded up to 16 + 4 (Win + 1) rounded
+ * up to 16: the tables first[r] = min{o : i0(o) >= r}, r = 0 ... n_in, of the rows and behind them of the columns, built on the device by every call.
+ * 16-byte aligned; its contents need not survive from one call to the next.
+ * The gradient is a gather over those tables: no atomics, two calls give the same bits; an image of y and of dx depends on its own image only.
+ * Limits: B Hin Win <= 2^30, B Hout Wout <= 2^30, ceil(pixels C / 256) <= 2^31 - 1.  Bad arguments -> MOGE_ERR_INVALID with a message naming the function
+ * and the argument, before anything is launched. */
+int moge_resize_bilinear_workspace(int B, int Hin, int Win, int Hout, int Wout, int C, int dtype, int64_t* forward_bytes, int64_t* backward_bytes);
+/* One launch. */
+int moge_resize_bilinear_forward(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int B, int Hin, int Win, int Hout, int Wout, int C, float scale_h, float scale_w,
+                                 void* workspace, void* stream);
+/* Two launches: the tables and the gather.  An input sample no output reads receives exactly 0. */
+int moge_resize_bilinear_backward(int dtype, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* workspace, int B, int Hin, int Win, int Hout, int Wout, int C,
+                                  float scale_h, float scale_w, void* stream);
+
+/* ---- trainable 1x1 convolution with few output channels, the exit of a head (python mirror moge_amd/resample.py conv1x1_narrow, csrc/resample_grad.hip,
+ * DESIGN.md section 23) ---------------------------------------------------------------------------------------------------------------------------
+ *   y[m,o] = bias[o] + sum_c x[m,c] w[o,c]      dx[m,c] = sum_o dy[m,o] w[o,c]      dw[o,c] = sum_m dy[m,o] x[m,c]      db[o] = sum_m dy[m,o]
+ * over the M = B H W pixels.  The conventions and the argument lists are those of moge_conv3x3_*, with these differences: 1 <= Cout <= 8 whatever its
+ * remainder, Cin a positive multiple of 16 bytes and at most 256; y and dy have a pixel stride of at least Cout elements and, like w, bias, dw and db, need
+ * only be aligned to their element (they are accessed element by element); x and dx keep the 16-byte rules.  w and dw are torch's contiguous
+ * (Cout, Cin, 1, 1).
+ * workspace: forward_bytes = 0 (not read, may be NULL); backward_bytes = 4 S Cout (Cin + 1) rounded up to 16, the fp32 partials of dw and db of
+ * S = ceil(M / ceil(M / S0)) slabs of pixels, S0 = max(1, min(ceil(M / 512), 1024)); needed where dw or db is asked for.
+ * No atomics: the slabs are added in slab order, so two calls give the same bits; a pixel of y and of dx depends on its own pixel only.
+ * Limits: B H W <= 2^30.  Bad arguments -> MOGE_ERR_INVALID with a message naming the function and the argument, before anything is launched.
+ * (The name: moge_conv1x1 is kept free, as the wide 1x1 convolution is moge_linear_* and has no entry of its own.) */
+int moge_narrow_conv1x1_workspace(int B, int H, int W, int Cin, int Cout, int dtype, int64_t* forward_bytes, int64_t* backward_bytes);
+/* bias may be NULL.  One launch. */
+int moge_narrow_conv1x1_forward(int dtype, const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, int B, int H, int W, int Cin, int Cout,
+                                void* workspace, void* stream);
+/* A NULL output is not computed (x is read for dw only, w for dx only).  One launch for dx, two for dw and db together. */
+int moge_narrow_conv1x1_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, void* workspace,
+                                 int B, int H, int W, int Cin, int Cout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

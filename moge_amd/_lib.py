@@ -251,6 +251,12 @@ SIGNATURES = {
     "moge_convt2x2_workspace": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "moge_convt2x2_forward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "moge_convt2x2_backward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_resize_bilinear_workspace": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    "moge_resize_bilinear_forward": (C.c_int, [_i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp]),
+    "moge_resize_bilinear_backward": (C.c_int, [_i32, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float, _vp]),
+    "moge_narrow_conv1x1_workspace": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    "moge_narrow_conv1x1_forward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "moge_narrow_conv1x1_backward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 

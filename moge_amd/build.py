@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmoge_hip.so")
 EXPERIMENTS_LIBDIR = os.path.join(LIBDIR, "experiments")     # build_experiments(): the -DMOGE_EXPERIMENTS copy the tests load beside LIB
-SOURCES = ["gemm.hip", "gemm_pp.hip", "conv_pp.hip", "l4c.hip", "attention.hip", "attention_pp.hip", "attention_grad.hip", "linear_grad.hip", "block_grad.hip", "conv_grad.hip", "convt_grad.hip", "elementwise.hip", "post.hip", "alignment.hip", "metrics.hip", "evaldata.hip", "traindata.hip", "refine.hip", "mesh.hip", "panorama.hip", "losses.hip", "optim.hip", "model_api.hip", "model_weights.hip", "model_encoder.hip", "model_v2.hip", "model_v1.hip", "tune.hip", "test_api.hip"]
+SOURCES = ["gemm.hip", "gemm_pp.hip", "conv_pp.hip", "l4c.hip", "attention.hip", "attention_pp.hip", "attention_grad.hip", "linear_grad.hip", "block_grad.hip", "conv_grad.hip", "convt_grad.hip", "resample_grad.hip", "elementwise.hip", "post.hip", "alignment.hip", "metrics.hip", "evaldata.hip", "traindata.hip", "refine.hip", "mesh.hip", "panorama.hip", "losses.hip", "optim.hip", "model_api.hip", "model_weights.hip", "model_encoder.hip", "model_v2.hip", "model_v1.hip", "tune.hip", "test_api.hip"]
 EXPERIMENT_SOURCES = ["conv_rb.hip"]      # tools/experiments/: the fused residual block (slower than the two conv_pp launches; kbench / A-B only)
 HEADERS = ["common.h", "launchers.h", "tune.h", "lr_sample.h", "quantile.h", "lds_image.h", "grad_host.h", "model_internal.h", "model_launch.h", os.path.join("..", "..", "include", "moge_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
