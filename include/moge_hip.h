@@ -866,6 +866,27 @@ int moge_conv3x3_forward(int dtype, const void* x, int64_t ldx, const void* w, c
 int moge_conv3x3_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, void* workspace, int B,
                           int H, int W, int Cin, int Cout, void* stream);
 
+/* ---- the decoder's residual block without norms, h = conv1(relu(x)), y = x + conv2(relu(h)): the 3x3 conv above with the ReLU in front of it and the
+ * skip add behind it fused into the conv's own kernels, forward and backward (python mirror moge_amd/resblock.py, csrc/conv_grad.hip, DESIGN.md
+ * section 24) -----------------------------------------------------------------------------------------------------------------------------------
+ * With conv, dgrad, wgrad the formulas of moge_conv3x3_* and relu(v) = v > 0 ? v : 0 on the STORED value, element by element (a positive subnormal
+ * passes and its mask is 1; -0 and +0 give 0 with mask 0; a NaN gives 0, where torch.relu keeps it):
+ *   forward:   y  = bias + conv(relu(x)) + res                      res (B, H, W, Cout) may be NULL
+ *   backward:  dx = (x > 0 ? dgrad(dy) : 0) + add                   add (B, H, W, Cin) may be NULL; the mask is a select, so an infinite or NaN sum
+ *                                                                   under a masked element gives 0
+ *              dw = wgrad(relu(x), dy)        db = the column sums of dy
+ * res and add go into the fp32 sum before its one rounding.  Without res / add the results have the bits of moge_conv3x3_* on relu(x), dx masked.
+ * Everything else is moge_conv3x3_*'s: the conventions, the checks and their words, the limits, B = 0, the launches per output, the splits of dw and
+ * db - and the WORKSPACE: there is no query of its own, the size is what moge_conv3x3_workspace gives for the same sizes (forward_bytes for the
+ * forward, backward_bytes for the backward), with the same layout.  res and add are pixel tensors like the others: 16-byte aligned, ldres / ldadd a
+ * multiple of 16 bytes and at least the channel count.  y must not overlap x, res or the weight, and dx must not overlap x, dy, add or the weight
+ * (the kernels read their inputs while other workgroups already store); this is not detected.
+ * x is required for dx (its mask) AND for dw; w for dx only.  Each of dx, dw, db may be NULL and then costs no launch. */
+int moge_relu_conv3x3_forward(int dtype, const void* x, int64_t ldx, const void* w, const void* bias, const void* res, int64_t ldres, void* y, int64_t ldy, int B, int H, int W,
+                              int Cin, int Cout, void* workspace, void* stream);
+int moge_relu_conv3x3_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, const void* add, int64_t ldadd, void* dx, int64_t lddx, void* dw,
+                               void* db, void* workspace, int B, int H, int W, int Cin, int Cout, void* stream);
+
 /* ---- trainable ConvTranspose2d(kernel 2, stride 2) of the decoder's conv_transpose resamplers and its gradients (python mirror moge_amd/convt.py,
  * csrc/convt_grad.hip) ---------------------------------------------------------------------------------------------------
  *   y [b, 2p+i, 2q+j, o] = bias[o] + sum_c x[b,p,q,c] w[c,o,i,j]                 i, j in {0, 1}

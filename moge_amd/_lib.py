@@ -248,6 +248,8 @@ SIGNATURES = {
     "moge_conv3x3_workspace": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "moge_conv3x3_forward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "moge_conv3x3_backward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "moge_relu_conv3x3_forward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "moge_relu_conv3x3_backward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "moge_convt2x2_workspace": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "moge_convt2x2_forward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "moge_convt2x2_backward": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

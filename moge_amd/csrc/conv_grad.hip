@@ -57,6 +57,12 @@ __device__ __forceinline__ void conv_load(u32x4 (&r)[4], const T* __restrict__ p
         if (ok && k < kend) r[i] = ldg16(p + ((long long)m[i] + dp * W + dq) * ld + k);
     }
 }
+// ReLU of the four chunks a thread holds (relu_chunk, lds_image.h), applied where they are staged and not where they are loaded, so that the loads stay
+// in flight across the MFMA loop; ReLU commutes with the gather
+template <typename T> __device__ __forceinline__ void relu_chunks(u32x4 (&r)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) r[i] = relu_chunk<T>(r[i]);
+}
 
 // does [m0, m1] hold an index that is 0 (hi false) or n - 1 (hi true) modulo n
 __device__ __forceinline__ bool range_hits(long long m0, long long m1, int n, bool hi) {
@@ -65,9 +71,14 @@ __device__ __forceinline__ bool range_hits(long long m0, long long m1, int n, bo
 }
 
 // forward (DG false): C = y, A = x, Kc = Cin, J = Cout.  dgrad (DG true): C = dx, A = dy, Kc = Cout, J = Cin.  wp: [tap][Cout][Cin].  M = B H W pixels.
-template <typename T, bool DG>
+// FUSE is the residual block's flavour (moge_relu_conv3x3_*); false is the plain conv, and X, E are not touched.
+//     forward:  A goes through ReLU before it is staged, and the epilogue adds the skip row E[m][o] where E is given:      y  = bias + conv(relu(x)) + res
+//     dgrad:    the epilogue selects by X[m][i], the conv's own input, and adds E[m][i] where E is given:       dx = (x > 0 ? dgrad(dy) : 0) + add
+// The contraction is the same code in the same order either way, so a fused result without E has the bits of the plain kernel on relu(x), or masked.
+template <typename T, bool DG, bool FUSE = false>
 __global__ __launch_bounds__(256) void conv_kernel(const T* __restrict__ A, long long lda, const T* __restrict__ wp, const T* __restrict__ bias, T* __restrict__ C,
-                                                   long long ldc, int M, int H, int W, int Kc, int J, int tiles_j) {
+                                                   long long ldc, int M, int H, int W, int Kc, int J, int tiles_j, const T* __restrict__ X, long long ldx,
+                                                   const T* __restrict__ E, long long lde) {
     constexpr int CH = TT<T>::CH;
     constexpr int BK = LCPR * CH;
     constexpr int NA = DG ? 5 : 3;
@@ -111,6 +122,7 @@ __global__ __launch_bounds__(256) void conv_kernel(const T* __restrict__ A, long
     lin_load<T, DG>(rb, wp + (axis_tap<DG>(0) * 3 + axis_tap<DG>(0)) * wtap, DG ? J : Kc, j0, J, 0, Kc, tid);
     while (true) {
         __syncthreads();                 // everyone finished reading the previous tile
+        if constexpr (FUSE && !DG) relu_chunks<T>(ra);
         lin_stage<T, false>(sA, ra, tid);
         lin_stage<T, DG>(sB, rb, tid);
         __syncthreads();
@@ -130,11 +142,12 @@ __global__ __launch_bounds__(256) void conv_kernel(const T* __restrict__ A, long
         opt = nopt;
         k0 = nk;
     }
-    lin_store<T, T>(acc, C, ldc, bias, i0, M, j0, J, wi, wj, l31, hi);
+    lin_store<T, T, FUSE ? (DG ? 2 : 1) : 0>(acc, C, ldc, bias, i0, M, j0, J, wi, wj, l31, hi, X, ldx, E, lde);
 }
 
 // part[z][tap][Cout][Cin] = sum over the pixels [z kper, min(M, (z + 1) kper)) of dy[m][o] x[src(m, tap)][i]; tap = blockIdx.y, z = blockIdx.z
-template <typename T>
+// RELU: the x chunks go through relu_chunks before they are staged (the fused residual block: dw = wgrad(relu(x), dy))
+template <typename T, bool RELU = false>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const T* __restrict__ dy, long long lddy, const T* __restrict__ x, long long ldx, float* __restrict__ part, int M,
                                                          int H, int W, int Cout, int Cin, int kper, int tiles_j) {
     constexpr int CH = TT<T>::CH;
@@ -184,6 +197,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const T* __restrict__ d
     for (int k0 = kbeg; k0 < kend; k0 += BK) {
         __syncthreads();
         lin_stage<T, true>(sA, ra, tid);
+        if constexpr (RELU) relu_chunks<T>(rb);
         lin_stage<T, true>(sB, rb, tid);
         __syncthreads();
         if (k0 + BK < kend) {
@@ -226,13 +240,13 @@ struct Conv3x3 {
     static void forward(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy, void* wp, int M, int H, int W, int Cin, int Cout, hipStream_t st) {
         repack<T>(w, wp, Cin, Cout, st);
         hipLaunchKernelGGL((conv_kernel<T, false>), dim3((unsigned)(tiles(M) * tiles(Cout))), dim3(256), 0, st, (const T*)x, (long long)ldx, (const T*)wp, (const T*)bias, (T*)y,
-                           (long long)ldy, M, H, W, Cin, Cout, (int)tiles(Cout));
+                           (long long)ldy, M, H, W, Cin, Cout, (int)tiles(Cout), (const T*)nullptr, 0LL, (const T*)nullptr, 0LL);
     }
     template <typename T>
     static void dgrad(const void* dy, int64_t lddy, const void* w, void* wp, void* dx, int64_t lddx, int M, int H, int W, int Cin, int Cout, hipStream_t st) {
         repack<T>(w, wp, Cin, Cout, st);
         hipLaunchKernelGGL((conv_kernel<T, true>), dim3((unsigned)(tiles(M) * tiles(Cin))), dim3(256), 0, st, (const T*)dy, (long long)lddy, (const T*)wp, (const T*)nullptr,
-                           (T*)dx, (long long)lddx, M, H, W, Cout, Cin, (int)tiles(Cin));
+                           (T*)dx, (long long)lddx, M, H, W, Cout, Cin, (int)tiles(Cin), (const T*)nullptr, 0LL, (const T*)nullptr, 0LL);
     }
     template <typename T>
     static void wgrad(const void* x, int64_t ldx, const void* dy, int64_t lddy, float* part, int M, int H, int W, int Cin, int Cout, int split, int kper, hipStream_t st) {
@@ -240,6 +254,37 @@ struct Conv3x3 {
                            (long long)ldx, part, M, H, W, Cout, Cin, kper, (int)tiles(Cin));
     }
 };
+
+// The residual block's flavour: the same constants, so the same workspace layout and the same splits of dw and db; wgrad reads relu(x).  Its forward and
+// dgrad take operands the plain conv does not have, so the entry points below launch them themselves.
+struct ReluConv3x3 : Conv3x3 {
+    template <typename T>
+    static void fused_forward(const void* x, int64_t ldx, const void* w, const void* bias, const void* res, int64_t ldres, void* y, int64_t ldy, void* wp, int M, int H, int W,
+                        int Cin, int Cout, hipStream_t st) {
+        repack<T>(w, wp, Cin, Cout, st);
+        hipLaunchKernelGGL((conv_kernel<T, false, true>), dim3((unsigned)(tiles(M) * tiles(Cout))), dim3(256), 0, st, (const T*)x, (long long)ldx, (const T*)wp, (const T*)bias,
+                           (T*)y, (long long)ldy, M, H, W, Cin, Cout, (int)tiles(Cout), (const T*)nullptr, 0LL, (const T*)res, (long long)ldres);
+    }
+    template <typename T>
+    static void fused_dgrad(const void* dy, int64_t lddy, const void* w, void* wp, const void* x, int64_t ldx, const void* add, int64_t ldadd, void* dx, int64_t lddx, int M, int H,
+                      int W, int Cin, int Cout, hipStream_t st) {
+        repack<T>(w, wp, Cin, Cout, st);
+        hipLaunchKernelGGL((conv_kernel<T, true, true>), dim3((unsigned)(tiles(M) * tiles(Cin))), dim3(256), 0, st, (const T*)dy, (long long)lddy, (const T*)wp, (const T*)nullptr,
+                           (T*)dx, (long long)lddx, M, H, W, Cout, Cin, (int)tiles(Cin), (const T*)x, (long long)ldx, (const T*)add, (long long)ldadd);
+    }
+    template <typename T>
+    static void wgrad(const void* x, int64_t ldx, const void* dy, int64_t lddy, float* part, int M, int H, int W, int Cin, int Cout, int split, int kper, hipStream_t st) {
+        hipLaunchKernelGGL((conv_wgrad_kernel<T, true>), dim3((unsigned)(tiles(Cout) * tiles(Cin)), 9, (unsigned)split), dim3(256), 0, st, (const T*)dy, (long long)lddy,
+                           (const T*)x, (long long)ldx, part, M, H, W, Cout, Cin, kper, (int)tiles(Cin));
+    }
+};
+
+template <typename T>
+void relu_conv_launch_backward(const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, const void* add, int64_t ldadd, void* dx, int64_t lddx, void* dw, void* db,
+                               char* ws, int M, int H, int W, int Cin, int Cout, int dtype, hipStream_t st) {
+    if (dx) ReluConv3x3::fused_dgrad<T>(dy, lddy, w, ws + conv_ws<ReluConv3x3>(M, Cin, Cout, dtype).wp, x, ldx, add, ldadd, dx, lddx, M, H, W, Cin, Cout, st);
+    conv_launch_backward<ReluConv3x3, T>(x, ldx, w, dy, lddy, nullptr, 0, dw, db, ws, M, H, W, Cin, Cout, dtype, st);      // dw from relu(x), db: the shared code
+}
 
 }  // namespace
 
@@ -257,6 +302,47 @@ int moge_conv3x3_forward(int dtype, const void* x, int64_t ldx, const void* w, c
 int moge_conv3x3_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, void* dx, int64_t lddx, void* dw, void* db, void* workspace, int B,
                           int H, int W, int Cin, int Cout, void* stream) {
     return conv_backward<Conv3x3>(dtype, x, ldx, w, dy, lddy, dx, lddx, dw, db, workspace, B, H, W, Cin, Cout, stream);
+}
+
+int moge_relu_conv3x3_forward(int dtype, const void* x, int64_t ldx, const void* w, const void* bias, const void* res, int64_t ldres, void* y, int64_t ldy, int B, int H, int W,
+                              int Cin, int Cout, void* workspace, void* stream) {
+    const char* fn = "moge_relu_conv3x3_forward";
+    if (int e = conv_check_sizes<ReluConv3x3>(fn, dtype, B, H, W, Cin, Cout)) return e;
+    if (B == 0) return 0;
+    if (int e = check_pixels(fn, "x", "ldx", x, ldx, Cin, dtype)) return e;
+    if (int e = check_vector(fn, "w", w, true)) return e;
+    if (int e = check_vector(fn, "bias", bias, false)) return e;
+    if (res)
+        if (int e = check_pixels(fn, "res", "ldres", res, ldres, Cout, dtype)) return e;
+    if (int e = check_pixels(fn, "y", "ldy", y, ldy, Cout, dtype)) return e;
+    if (int e = check_vector(fn, "workspace", workspace, true)) return e;
+    if (dtype == MOGE_FP16) ReluConv3x3::fused_forward<f16>(x, ldx, w, bias, res, ldres, y, ldy, workspace, B * H * W, H, W, Cin, Cout, (hipStream_t)stream);
+    else ReluConv3x3::fused_forward<float>(x, ldx, w, bias, res, ldres, y, ldy, workspace, B * H * W, H, W, Cin, Cout, (hipStream_t)stream);
+    return launched("moge_relu_conv3x3_forward: launch failed");
+}
+
+int moge_relu_conv3x3_backward(int dtype, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, const void* add, int64_t ldadd, void* dx, int64_t lddx, void* dw,
+                               void* db, void* workspace, int B, int H, int W, int Cin, int Cout, void* stream) {
+    const char* fn = "moge_relu_conv3x3_backward";
+    if (int e = conv_check_sizes<ReluConv3x3>(fn, dtype, B, H, W, Cin, Cout)) return e;
+    if (B == 0 || (!dx && !dw && !db)) return 0;
+    if (int e = check_pixels(fn, "dy", "lddy", dy, lddy, Cout, dtype)) return e;
+    if (dx || dw)                                                        // x is the mask of dx and, through ReLU, the operand of dw
+        if (int e = check_pixels(fn, "x", "ldx", x, ldx, Cin, dtype)) return e;
+    if (dx) {
+        if (int e = check_vector(fn, "w", w, true)) return e;
+        if (add)
+            if (int e = check_pixels(fn, "add", "ldadd", add, ldadd, Cin, dtype)) return e;
+        if (int e = check_pixels(fn, "dx", "lddx", dx, lddx, Cin, dtype)) return e;
+    }
+    if (int e = check_vector(fn, "dw", dw, false)) return e;
+    if (int e = check_vector(fn, "db", db, false)) return e;
+    if (int e = check_vector(fn, "workspace", workspace, true)) return e;
+    if (dtype == MOGE_FP16)
+        relu_conv_launch_backward<f16>(x, ldx, w, dy, lddy, add, ldadd, dx, lddx, dw, db, (char*)workspace, B * H * W, H, W, Cin, Cout, dtype, (hipStream_t)stream);
+    else
+        relu_conv_launch_backward<float>(x, ldx, w, dy, lddy, add, ldadd, dx, lddx, dw, db, (char*)workspace, B * H * W, H, W, Cin, Cout, dtype, (hipStream_t)stream);
+    return launched("moge_relu_conv3x3_backward: launch failed");
 }
 
 }  // extern "C"

@@ -114,10 +114,22 @@ __device__ __forceinline__ void lin_zero(f32x16 (&acc)[2][2]) {
             for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
 }
 
-// the tile's part of C (I, J), plus bias[j] where there is one: the row of C on the lane, four consecutive columns per store
-template <typename TO, typename TB>
+// ReLU of a 16-byte chunk as the fused residual block defines it (conv_grad.hip), on the STORED value: v > 0 ? v : 0 for every
+// element, so a positive subnormal passes unchanged, -0 and +0 give 0 and a NaN gives 0 (torch.relu keeps a NaN)
+template <typename T> __device__ __forceinline__ u32x4 relu_chunk(const u32x4& r) {
+    typename Vec<T>::type v = __builtin_bit_cast(typename Vec<T>::type, r);
+#pragma unroll
+    for (int e = 0; e < TT<T>::CH; e++) v[e] = v[e] > (T)0 ? v[e] : (T)0;
+    return __builtin_bit_cast(u32x4, v);
+}
+
+// the tile's part of C (I, J), plus bias[j] where there is one: the row of C on the lane, four consecutive columns per store.  EPI 0 is that alone.
+// EPI 1 (the fused block's forward): plus E[i][j] where E is given - the skip row, added to the fp32 sum before its one rounding.
+// EPI 2 (the fused block's dgrad): X[i][j] > 0 ? sum : 0 - a select, so that an infinite or NaN sum under a masked element gives 0 - plus E[i][j] where
+// E is given.  X and E are read four columns at a time through their own row strides, inside [0, I) x [0, J) only.
+template <typename TO, typename TB, int EPI = 0>
 __device__ __forceinline__ void lin_store(const f32x16 (&acc)[2][2], TO* __restrict__ C, long long ldc, const TB* __restrict__ bias, int i0, int I, int j0, int J, int wi, int wj,
-                                          int l31, int hi) {
+                                          int l31, int hi, const TO* __restrict__ X = nullptr, long long ldx = 0, const TO* __restrict__ E = nullptr, long long lde = 0) {
 #pragma unroll
     for (int a = 0; a < 2; a++) {
         const int i = i0 + wi + a * 32 + l31;
@@ -131,7 +143,24 @@ __device__ __forceinline__ void lin_store(const f32x16 (&acc)[2][2], TO* __restr
                 if (j >= J) continue;                                   // J is a multiple of 4: a group of four is inside or outside
                 float bv[4] = {0.f, 0.f, 0.f, 0.f};
                 if (bias) load4(bias + j, bv);
-                store4(crow + j, acc[a][b][4 * g4] + bv[0], acc[a][b][4 * g4 + 1] + bv[1], acc[a][b][4 * g4 + 2] + bv[2], acc[a][b][4 * g4 + 3] + bv[3]);
+                if constexpr (EPI == 0) {
+                    store4(crow + j, acc[a][b][4 * g4] + bv[0], acc[a][b][4 * g4 + 1] + bv[1], acc[a][b][4 * g4 + 2] + bv[2], acc[a][b][4 * g4 + 3] + bv[3]);
+                } else {
+                    float v[4] = {acc[a][b][4 * g4] + bv[0], acc[a][b][4 * g4 + 1] + bv[1], acc[a][b][4 * g4 + 2] + bv[2], acc[a][b][4 * g4 + 3] + bv[3]};
+                    if constexpr (EPI == 2) {
+                        float xv[4];
+                        load4(X + i * ldx + j, xv);
+#pragma unroll
+                        for (int e = 0; e < 4; e++) v[e] = xv[e] > 0.f ? v[e] : 0.f;
+                    }
+                    if (E) {
+                        float ev[4];
+                        load4(E + i * lde + j, ev);
+#pragma unroll
+                        for (int e = 0; e < 4; e++) v[e] += ev[e];
+                    }
+                    store4(crow + j, v[0], v[1], v[2], v[3]);
+                }
             }
     }
 }
